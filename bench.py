@@ -15,8 +15,12 @@ is not set -- this process starts the N ranks itself as child processes BEFORE a
 rank 0's line.  `--mode train` times the stage-2 training step instead (BASELINE configs[2] at N=1: scene + interactee,
 B=64/GPU, 20 000-point scenes; configs[3] at N>1: config_mld_gimo, scene only), with the gradient all-reduce over RCCL.
 
-Prints ONE JSON line on rank 0 (contract in the task description), with `roofline` (dominant kernel,
-timed with events on its own stream) and `cpu_baseline` (the PyTorch-CPU oracle on the host cores, N=1 only).
+Prints ONE JSON line on rank 0 (contract in the task description), with `roofline` (dominant kernel, timed with events
+around it inside the timed steps; under --graph only with --full, see below).  A plain run sets up, warms up, times the steps and prints that line; `--full` adds what
+takes runs of its own: at N=1 `mpjpe_vs_ref` / `parity_mode` (the MPJPE gate and the fp32 parity path timed the same way),
+`cpu_baseline` (the PyTorch-CPU oracle on the host cores) and `cfg1_vae_reconstruct`, and under --graph the eager passes
+that time the sampling kernel for `roofline`.  `--dump-outputs DIR` writes what the last timed step computed (rank 0) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -53,6 +57,14 @@ def build_models(dev, weight_dtype, vae_precision="fp32"):
                         clip_sample=False, set_alpha_to_one=False, steps_offset=1)
     sch.set_timesteps(DDIM_STEPS)
     return vae, den, sch
+
+
+def make_inputs(B, rank, dev):
+    """The seeded synthetic batch of one rank: interactee motion [B,196,132], initial latents [B,1,256], lengths."""
+    g = torch.Generator(device="cpu").manual_seed(1234 + rank)
+    motion = torch.randn(B, T_FRAMES, NFEATS, generator=g).to(dev)
+    latents = torch.randn(B, 1, 256, generator=g).to(dev)
+    return motion, latents, [T_FRAMES] * B
 
 
 def one_pass(vae, den, sch, motion, latents, lengths, ev=None):
@@ -225,6 +237,62 @@ def mpjpe_check(dev, weights, vae_prec, B):
                   "per_batch_delta_mm"}
 
 
+DUMP_BYTES = 64_000_000     # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every {name: tensor} as <path>/<name>.npy in float32, at most DUMP_BYTES in all.  Arrays are taken
+    smallest first, each against an even share of what is left; one over its share is cut to a fixed, seeded sample of its
+    leading-axis rows (of its elements, flattened, when a single row is over the share), sorted; <name>_rows.npy then
+    holds those indices (float64)."""
+    os.makedirs(path, exist_ok=True)
+    items = sorted(((n, t.detach().float().cpu().numpy()) for n, t in arrays.items()), key=lambda kv: kv[1].nbytes)
+    left = DUMP_BYTES
+    for i, (name, a) in enumerate(items):
+        share = left // (len(items) - i)
+        if a.nbytes > share:
+            if a.nbytes // a.shape[0] + 8 > share:
+                a = a.reshape(-1)
+            k = share // (a.nbytes // a.shape[0] + 8)
+            assert k > 0, f"--dump-outputs: {name} does not fit in {share} bytes"
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], k, replace=False)).astype(np.float64)
+            a = a[rows.astype(np.int64)]
+            np.save(os.path.join(path, name + "_rows.npy"), rows)
+            left -= rows.nbytes
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+
+
+def sampling_roofline(den, dev, weights, B, n_infer, loop_ms):
+    """`roofline` of the sample mode: the persistent DDIM kernel, loop_ms per launch."""
+    alg_bytes = den_algorithmic_bytes(den, B, 1, n_infer)
+    achieved = alg_bytes / (loop_ms * 1e-3) / 1e9
+    from seeme_amd.mld_denoiser import _device_cus
+    Cc, spc = den._cluster_plan(B, 1, False, False, _device_cus(dev))
+    if Cc:          # one sample (or, above B = 64, up to 8) split over Cc CUs: a CU streams its slices + the replicated FFN matrices
+        exe_cu = den_cluster_bytes_per_cu(den, Cc, n_infer)
+        cus = ((B + spc - 1) // spc + 7) // 8 * 8 * Cc
+        exe_bytes = exe_cu * cus
+        kname = (f"k_den_cluster (persistent DDIM loop, one sample split over {Cc} CUs)" if spc == 1 else
+                 f"k_den_cluster_ms (persistent loop, clusters of {Cc} CUs that own {spc} samples each)")
+    else:
+        exe_bytes = exe_cu = den_executed_bytes(den, B, 1, n_infer)
+        cus = min(B, 256)                               # one workgroup (one CU) per sample chain
+        kname = "k_den_sample (persistent DDIM loop, one CU per sample)"
+    per_cu = exe_cu / (loop_ms * 1e-3) / 1e9            # every CU streams its bytes itself (from L2 / Infinity Cache)
+    return {"bound": "hbm", "kernel": kname,
+            "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": measured_traffic(weights, B, n_infer, Cc if spc == 1 else 0) if spc == 1 else None,
+            "traffic_source": "profiles/traffic.json (rocprofv3 --pmc passes of this configuration; a committed constant, not observed in this run)",
+            "ms_per_launch": round(loop_ms, 4), "algorithmic_bytes_per_launch": int(alg_bytes),
+            # what the CUs actually stream (from L2 / Infinity Cache, never HBM: the image is 9-20 MB) and how close
+            # each CU's L1 fill path runs to its measured ceiling of 118 GB/s (scripts/stream_probe3.py)
+            "executed_bytes_per_launch": int(exe_bytes),
+            "per_cu_stream": {"achieved": round(per_cu, 2), "peak": 118.0, "unit": "GB/s per CU",
+                              "frac": round(per_cu / 118.0, 4), "cus_busy": cus}}
+
+
 def spawn_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: start the N ranks as children of this process, which has not
     touched the GPU (no HIP call, no torch.cuda.is_available()) and never will; rank 0 prints the JSON line on the
@@ -332,6 +400,10 @@ def train_mode(args, dev, rank, world, backend, dist_on):
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = float(tt.item())
     assert torch.isfinite(loss.detach()).all()
+    if args.dump_outputs and rank == 0:
+        # the loss of the last step and every trainable tensor after its update, flattened in parameter order
+        dump_outputs(args.dump_outputs, {"loss": loss, "params": torch.cat([p.detach().reshape(-1).float()
+                                                                          for p in model.trainable_parameters()])})
     if with_scene:
         model.proscene.scene_enc.timing_events = None
     res = {
@@ -395,8 +467,15 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="sequences per GPU per pass (BASELINE configs[1]: 32)")
     ap.add_argument("--weights", default="fp16", choices=["fp32", "bf16", "fp16"], help="denoiser weight image dtype")
     ap.add_argument("--vae", default="fp16", choices=["fp32", "fp16"], help="VAE MFMA operand type (fp32 = exact parity path)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity-check", action="store_true", help="skip the MPJPE-vs-fp32-path check and the fp32 timing")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: MPJPE gate + fp32 parity timing, CPU baseline, VAE-reconstruct "
+                         "leg (N=1), and under --graph the eager passes that time the sampling kernel: a plain --graph run "
+                         "prints no roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32, at most 64 MB in all: "
+                         "feats (decoded motion) when sampling; loss and params (trainable tensors after the update) in train mode")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and the VAE-reconstruct leg")
+    ap.add_argument("--no-parity-check", action="store_true", help="--full without the MPJPE-vs-fp32-path check and the fp32 timing")
     ap.add_argument("--streams", type=int, default=1,
                     help="HIP streams the passes are dealt over (each with its own model instance); 1 = the named configuration, "
                          ">1 = several B-sized batches in flight on one GPU (a B=32 pass occupies 32 of 256 CUs)")
@@ -413,6 +492,8 @@ def main():
                     help="CUs per sample in the sampling kernel (default: the model's policy, 8 / 4 / 2 while B x C <= 256; 0 = one CU per sample)")
     ap.add_argument("--scheduler", default="ddim", choices=["ddim", "ddpm"], help="ddpm = 1000-step ancestral sampling (BASELINE configs[4])")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.mode == "train" and args.batch == 32 and "--batch" not in sys.argv:
         args.batch = 64                                     # BASELINE configs[2] / [3]: 64 sequences per GPU
 
@@ -466,10 +547,7 @@ def main():
         sch.set_timesteps(1000)
         n_infer = 1000
         models = [(v, d, sch) for v, d, _ in models]
-    g = torch.Generator(device="cpu").manual_seed(1234 + rank)
-    motion = torch.randn(B, T_FRAMES, NFEATS, generator=g).to(dev)
-    latents = torch.randn(B, 1, 256, generator=g).to(dev)
-    lengths = [T_FRAMES] * B
+    motion, latents, lengths = make_inputs(B, rank, dev)
 
     def run_pass(i, ev=None):
         v, d, sc = models[i % S]
@@ -521,30 +599,19 @@ def main():
     for _, d, _ in models:                                  # no cluster of the sampling kernel may have given up waiting for a peer
         code, _local = d.cluster_status()
         assert code == 0, f"k_den_cluster: exchange timed out (code {code}): the results of this run are invalid"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"feats": out})     # decoded motion features [B,196,132] of the last timed step
 
     # dominant kernel: the persistent DDIM kernel
     loop_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
-    if args.graph:      # events bracket whole replays there: take the kernel time from the eager warm-up instead
-        for _ in range(2):  # (the first eager pass after the capture allocates its tables outside the graph's pool: timed on the second)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            one_pass(vae, den, sch, motion, latents, lengths, (e0, e1))
-            torch.cuda.synchronize()
-        loop_ms = e0.elapsed_time(e1)
-    alg_bytes = den_algorithmic_bytes(den, B, 1, n_infer)
-    achieved = alg_bytes / (loop_ms * 1e-3) / 1e9
-    from seeme_amd.mld_denoiser import _device_cus
-    Cc, spc = den._cluster_plan(B, 1, False, False, _device_cus(dev))
-    if Cc:          # one sample (or, above B = 64, up to 8) split over Cc CUs: a CU streams its slices + the replicated FFN matrices
-        exe_cu = den_cluster_bytes_per_cu(den, Cc, n_infer)
-        cus = ((B + spc - 1) // spc + 7) // 8 * 8 * Cc
-        exe_bytes = exe_cu * cus
-        kname = (f"k_den_cluster (persistent DDIM loop, one sample split over {Cc} CUs)" if spc == 1 else
-                 f"k_den_cluster_ms (persistent loop, clusters of {Cc} CUs that own {spc} samples each)")
-    else:
-        exe_bytes = exe_cu = den_executed_bytes(den, B, 1, n_infer)
-        cus = min(B, 256)                               # one workgroup (one CU) per sample chain
-        kname = "k_den_sample (persistent DDIM loop, one CU per sample)"
-    per_cu = exe_cu / (loop_ms * 1e-3) / 1e9            # every CU streams its bytes itself (from L2 / Infinity Cache)
+    if args.graph:      # events bracket whole replays there: take the kernel time from eager passes instead (--full only)
+        loop_ms = None
+        if args.full:
+            for _ in range(2):  # (the first eager pass after the capture allocates its tables outside the graph's pool: timed on the second)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                one_pass(vae, den, sch, motion, latents, lengths, (e0, e1))
+                torch.cuda.synchronize()
+            loop_ms = e0.elapsed_time(e1)
 
     if rank == 0:
         res = {
@@ -568,18 +635,10 @@ def main():
                        "batch_per_gpu": B, "seq_len": T_FRAMES, "ddim_steps": n_infer,
                        "parallelism": f"dp{world} (independent shards, no collective on the data path)"
                                       + (f", {S} batches in flight per GPU" if S > 1 else "") + (", hipGraph replay" if args.graph else "")},
-            "roofline": {"bound": "hbm", "kernel": kname,
-                         "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": measured_traffic(args.weights, B, n_infer, Cc if spc == 1 else 0) if spc == 1 else None,
-                         "traffic_source": "profiles/traffic.json (rocprofv3 --pmc passes of this configuration; a committed constant, not observed in this run)",
-                         "ms_per_launch": round(loop_ms, 4), "algorithmic_bytes_per_launch": int(alg_bytes),
-                         # what the CUs actually stream (from L2 / Infinity Cache, never HBM: the image is 9-20 MB) and how close
-                         # each CU's L1 fill path runs to its measured ceiling of 118 GB/s (scripts/stream_probe3.py)
-                         "executed_bytes_per_launch": int(exe_bytes),
-                         "per_cu_stream": {"achieved": round(per_cu, 2), "peak": 118.0, "unit": "GB/s per CU",
-                                           "frac": round(per_cu / 118.0, 4), "cus_busy": cus}},
         }
-        if world == 1 and S == 1 and not args.graph and args.scheduler == "ddim" and not args.no_parity_check:
+        if loop_ms is not None:
+            res["roofline"] = sampling_roofline(den, dev, args.weights, B, n_infer, loop_ms)
+        if args.full and world == 1 and S == 1 and not args.graph and args.scheduler == "ddim" and not args.no_parity_check:
             res["mpjpe_vs_ref"] = mpjpe_check(dev, args.weights, args.vae, B)
             if not (args.weights == "fp32" and args.vae == "fp32"):      # the parity configuration, timed the same way
                 pv, pd, ps = build_models(dev, "fp32", "fp32")
@@ -591,7 +650,7 @@ def main():
                     one_pass(pv, pd, ps, motion, latents, lengths)
                 torch.cuda.synchronize()
                 res["parity_mode"] = {"dtype": "f32", "value": round(B * args.steps / (time.perf_counter() - tp), 2), "unit": "seqs/s"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(B)
             # the GPU side of BASELINE configs[0] (VAE reconstruct, B = 4), fp32 parity path, beside its CPU leg
             pv = build_models(dev, "fp32", "fp32")[0]

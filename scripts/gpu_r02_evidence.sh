@@ -3,9 +3,9 @@
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT && T=${1:-r02} && mkdir -p gpurun_out/$T && O=gpurun_out/$T
 timeout -k 10 900 python -m pytest tests -q -m gpu > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $O/pytest_gpu.log
-timeout -k 10 300 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
-timeout -k 10 300 python bench.py --weights fp32 --vae fp32 --no-cpu-baseline > $O/bench_fp32.json 2>/dev/null
-timeout -k 10 300 python bench.py --batch 256 --no-cpu-baseline > $O/bench_B256.json 2>/dev/null
+timeout -k 10 300 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+timeout -k 10 300 python bench.py --full --weights fp32 --vae fp32 --no-cpu-baseline > $O/bench_fp32.json 2>/dev/null
+timeout -k 10 300 python bench.py --full --batch 256 --no-cpu-baseline > $O/bench_B256.json 2>/dev/null
 timeout -k 10 300 python bench.py --mode train --steps 20 > $O/bench_train_scene.json 2>/dev/null
 timeout -k 10 300 python bench.py --mode train --train-config gimo --steps 20 > $O/bench_train_gimo.json 2>/dev/null
 SEEME_BENCH_BACKEND=gloo SEEME_BENCH_DEVICE=0 timeout -k 10 300 python bench.py --gpus 2 --no-cpu-baseline > $O/bench_gloo2.json 2>/dev/null

@@ -3,10 +3,10 @@
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT && T=${1:-r03} && mkdir -p gpurun_out/$T && O=gpurun_out/$T
 timeout -k 10 1000 python -m pytest tests -q -m gpu > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $O/pytest_gpu.log
-timeout -k 10 300 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+timeout -k 10 300 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
 timeout -k 10 300 python bench.py --cluster 0 --no-cpu-baseline --no-parity-check > $O/bench_one_cu_per_sample.json 2>/dev/null
 timeout -k 10 300 python bench.py --weights fp32 --vae fp32 --no-cpu-baseline --no-parity-check > $O/bench_fp32.json 2>/dev/null
-timeout -k 10 300 python bench.py --weights bf16 --no-cpu-baseline > $O/bench_bf16.json 2>/dev/null
+timeout -k 10 300 python bench.py --full --weights bf16 --no-cpu-baseline > $O/bench_bf16.json 2>/dev/null
 timeout -k 10 300 python bench.py --batch 64 --no-cpu-baseline --no-parity-check > $O/bench_B64.json 2>/dev/null
 timeout -k 10 300 python bench.py --batch 128 --no-cpu-baseline --no-parity-check > $O/bench_B128.json 2>/dev/null
 timeout -k 10 300 python bench.py --batch 256 --no-cpu-baseline --no-parity-check > $O/bench_B256.json 2>/dev/null
@@ -14,8 +14,8 @@ timeout -k 10 300 python bench.py --batch 512 --no-cpu-baseline --no-parity-chec
 SEEME_DEN_CLUSTER_MS=0 timeout -k 10 300 python bench.py --batch 128 --no-cpu-baseline --no-parity-check > $O/bench_B128_no_ms.json 2>/dev/null
 SEEME_DEN_CLUSTER_MS=0 timeout -k 10 300 python bench.py --batch 256 --no-cpu-baseline --no-parity-check > $O/bench_B256_no_ms.json 2>/dev/null
 SEEME_DEN_CLUSTER_MS=0 timeout -k 10 300 python bench.py --batch 512 --no-cpu-baseline --no-parity-check > $O/bench_B512_no_ms.json 2>/dev/null
-SEEME_DEN_CLUSTER_MS=0 timeout -k 10 300 python bench.py --scheduler ddpm --batch 512 --graph --steps 3 --warmup 1 --no-cpu-baseline --no-parity-check > $O/bench_ddpm1000_B512_no_ms.json 2>/dev/null
-timeout -k 10 300 python bench.py --scheduler ddpm --batch 512 --graph --steps 3 --warmup 1 --no-cpu-baseline --no-parity-check > $O/bench_ddpm1000_B512.json 2>/dev/null
+SEEME_DEN_CLUSTER_MS=0 timeout -k 10 300 python bench.py --full --scheduler ddpm --batch 512 --graph --steps 3 --warmup 1 --no-cpu-baseline --no-parity-check > $O/bench_ddpm1000_B512_no_ms.json 2>/dev/null
+timeout -k 10 300 python bench.py --full --scheduler ddpm --batch 512 --graph --steps 3 --warmup 1 --no-cpu-baseline --no-parity-check > $O/bench_ddpm1000_B512.json 2>/dev/null
 timeout -k 10 300 python bench.py --mode train --steps 20 > $O/bench_train_scene.json 2>/dev/null
 timeout -k 10 300 python bench.py --mode train --train-config gimo --steps 20 > $O/bench_train_gimo.json 2>/dev/null
 SEEME_BENCH_BACKEND=gloo SEEME_BENCH_DEVICE=0 timeout -k 10 300 python bench.py --gpus 2 --no-cpu-baseline --no-parity-check > $O/bench_gloo2.json 2>/dev/null

@@ -572,7 +572,7 @@ def test_vae_hip_training_dropout_matches_twin_with_same_masks(dev):
 
 
 @pytest.mark.parametrize("argv,checks", [
-    (["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-parity-check", "--streams", "2", "--graph"],
+    (["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-parity-check", "--streams", "2", "--graph", "--full"],
      {"metric": "sampled seqs/sec (T=196, 50 DDIM steps)", "n_gpus": 1}),
     (["--steps", "2", "--warmup", "1", "--mode", "train", "--train-config", "gimo", "--points", "2048"],
      {"n_gpus": 1}),
@@ -600,6 +600,61 @@ def test_bench_modes_emit_the_contract_line(dev, argv, checks):
     assert d["roofline"]["bound"] in ("hbm", "mfma") and 0 < d["roofline"]["frac"] < 1
     for k, v in checks.items():
         assert d[k] == v, (k, d[k])
+
+
+def test_bench_plain_run_dumps_reproducible_outputs(dev, tmp_path):
+    """A plain bench.py run (no --full) prints the headline line without the legs that take runs of their own, and
+    --dump-outputs writes the decoded features of the last timed step: float32 [B,196,132], the same in two processes and
+    the same as one pass of bench's own models on bench's seeded inputs in this process.  The --streams 2 --graph path
+    (replayed graph outputs, one model per stream, one CU per sample) dumps what that configuration computes; train mode
+    dumps the last loss and the trainable tensors after their update."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+
+    def run(tag, extra):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "8",
+                            "--dump-outputs", str(tmp_path / tag)] + extra, capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0])
+
+    outs = []
+    for tag in ("a", "b"):
+        d = run(tag, [])
+        assert d["metric"] == "sampled seqs/sec (T=196, 50 DDIM steps)" and d["unit"] == "seqs/s" and d["higher_is_better"] is True
+        assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and "dtype" in d and "roofline" in d
+        for k in ("mpjpe_vs_ref", "parity_mode", "cpu_baseline", "cfg1_vae_reconstruct"):
+            assert k not in d, k
+        assert sorted(os.listdir(tmp_path / tag)) == ["feats.npy"]
+        outs.append(np.load(tmp_path / tag / "feats.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (8, 196, 132) and np.isfinite(outs[0]).all()
+    assert np.array_equal(outs[0], outs[1])
+
+    motion, latents, lengths = bench.make_inputs(8, 0, dev)
+    vae, den, sch = bench.build_models(dev, "fp16", "fp16")
+    ref = bench.one_pass(vae, den, sch, motion, latents, lengths).cpu().numpy()
+    err = float(np.abs(outs[0] - ref).max()) / float(np.abs(ref).max())
+    print("dump vs in-process pass: rel err", err)
+    assert err < 1e-5, err
+
+    d = run("g", ["--streams", "2", "--graph"])
+    assert "roofline" not in d                                   # under --graph the kernel time needs --full
+    den.cluster, den.pack_xcds = 0, 8                            # what bench sets for more than one stream
+    ref1 = bench.one_pass(vae, den, sch, motion, latents, lengths).cpu().numpy()
+    g = np.load(tmp_path / "g" / "feats.npy")
+    err = float(np.abs(g - ref1).max()) / float(np.abs(ref1).max())
+    print("--streams 2 --graph dump vs in-process pass: rel err", err)
+    assert g.shape == (8, 196, 132) and err < 1e-5, err
+
+    run("t", ["--mode", "train", "--train-config", "vae"])
+    assert sorted(os.listdir(tmp_path / "t")) == ["loss.npy", "params.npy"]
+    loss, params = np.load(tmp_path / "t" / "loss.npy"), np.load(tmp_path / "t" / "params.npy")
+    assert loss.size == 1 and np.isfinite(loss).all() and params.dtype == np.float32 and params.ndim == 1
+    assert params.size > 1_000_000 and np.isfinite(params).all()
 
 
 def test_launch_mapping_knobs_do_not_change_results(dev, tmp_path):
@@ -663,7 +718,7 @@ def test_cfg5_ddpm1000_at_its_own_size(dev):
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--scheduler", "ddpm", "--batch", "512", "--graph", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-parity-check"], capture_output=True, text=True, timeout=900, env=env)
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--no-parity-check"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert "1000 DDPM steps" in d["metric"] and d["config"]["batch_per_gpu"] == 512 and d["config"]["ddim_steps"] == 1000

@@ -122,8 +122,9 @@ def test_timestep_features_match_oracle():
     assert rel_err(timestep_features(t).numpy(), O.timestep_features(t.numpy())) < 1e-4
 
 
-def test_config_loader_own_and_reference_yaml():
-    from seeme_amd.config import parse_config, instantiate_from_config
+def test_config_loader_own_and_reference_yaml(tmp_path):
+    import yaml
+    from seeme_amd.config import TARGET_MAP, parse_config, instantiate_from_config
     cfg = parse_config(os.path.join(REPO, "configs", "config_mld_scene.yaml"))
     assert cfg.model.condition == ["text", "scene", "interactee"]
     assert cfg.model.denoiser.params.ablation.MD_TRANS is True
@@ -132,14 +133,35 @@ def test_config_loader_own_and_reference_yaml():
     den = instantiate_from_config(cfg.model.denoiser)
     sch = instantiate_from_config(cfg.model.scheduler)
     assert type(den).__name__ == "MldDenoiser" and type(sch).__name__ == "DDIMScheduler"
-    ref = "/root/reference/configs/config_mld_egobody.yaml"       # only in the build container
-    if os.path.exists(ref):
-        r = parse_config(ref)
-        assert r.model.denoiser.target == "mld.models.architectures.mld_denoiser.MldDenoiser"   # file untouched
-        assert type(instantiate_from_config(r.model.denoiser)).__module__ == "seeme_amd.mld_denoiser"
-        assert type(instantiate_from_config(r.model.motion_vae)).__module__ == "seeme_amd.mld_vae"
-        assert type(instantiate_from_config(r.model.scheduler)).__module__ == "seeme_amd.schedulers"
-        assert r.model.scheduler.num_inference_timesteps == 50
+    # the same tree in the reference's layout, every module `target` spelled with the reference's class path
+    ref_target = {v: k for k, v in TARGET_MAP.items()}
+    for fn in ("base.yaml", "config_mld_egobody.yaml"):
+        (tmp_path / fn).write_text(open(os.path.join(REPO, "configs", fn)).read())
+    os.makedirs(tmp_path / "modules")
+    for fn in os.listdir(os.path.join(REPO, "configs", "modules")):
+        node = yaml.safe_load(open(os.path.join(REPO, "configs", "modules", fn)))
+        for v in node.values():
+            if isinstance(v, dict) and v.get("target") in ref_target:
+                v["target"] = ref_target[v["target"]]
+        (tmp_path / "modules" / fn).write_text(yaml.safe_dump(node))
+    # loader semantics the layout relies on: an assets.yaml merged last, a module whose target this package does not
+    # provide, and references to keys no file defines -- resolved lazily by OmegaConf, so kept as written here
+    (tmp_path / "assets.yaml").write_text("FOLDER: ./runs\nmodel:\n  asset_path: ./deps/asset\n")
+    (tmp_path / "modules" / "zz_unmapped.yaml").write_text(
+        "probe:\n  target: pkg.unmapped.Probe\n  params:\n    path: ${model.asset_path}\n    size: ${model.undefined_node.size}\n"
+        "    label: size ${model.undefined_node.size} of ${model.nfeats}\n")
+    r = parse_config(str(tmp_path / "config_mld_egobody.yaml"))
+    assert r.FOLDER == "./runs" and r.model.asset_path == "./deps/asset"
+    assert r.model.probe.target == "pkg.unmapped.Probe" and r.model.probe.params.path == "./deps/asset"
+    assert r.model.probe.params.size == "${model.undefined_node.size}"
+    assert r.model.probe.params.label == "size ${model.undefined_node.size} of ${model.nfeats}"
+    assert r.model.denoiser.target == "mld.models.architectures.mld_denoiser.MldDenoiser"   # kept as written
+    assert r.model.motion_vae.target == "mld.models.architectures.mld_vae.MldVae"
+    assert r.model.scheduler.target == "diffusers.DDIMScheduler"
+    assert type(instantiate_from_config(r.model.denoiser)).__module__ == "seeme_amd.mld_denoiser"
+    assert type(instantiate_from_config(r.model.motion_vae)).__module__ == "seeme_amd.mld_vae"
+    assert type(instantiate_from_config(r.model.scheduler)).__module__ == "seeme_amd.schedulers"
+    assert r.model.scheduler.num_inference_timesteps == 50
 
 
 def test_mld_constructs_from_config_on_cpu():
@@ -400,3 +422,37 @@ def test_cluster_weight_image_indexing():
                 assert img[u, w, i, lane, e] == W[row, col]
             # every element appears exactly once
             assert torch.equal(torch.sort(img.reshape(-1))[0], torch.sort(W.reshape(-1))[0])
+
+
+def test_bench_dump_outputs_float32_and_seeded_sample_over_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array as <name>.npy in float32; one over the byte budget is cut to a fixed, seeded,
+    sorted sample of its rows, whose indices land in <name>_rows.npy."""
+    import bench
+    x = torch.arange(10 * 6, dtype=torch.float16).reshape(10, 2, 3)
+    bench.dump_outputs(str(tmp_path / "a"), {"feats": x})
+    a = np.load(tmp_path / "a" / "feats.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, x.float().numpy())
+    assert sorted(os.listdir(tmp_path / "a")) == ["feats.npy"]
+    monkeypatch.setattr(bench, "DUMP_BYTES", 100)          # 24 bytes per row + 8 per index: 3 of the 10 rows
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"feats": x})
+    rows = np.load(tmp_path / "b" / "feats_rows.npy")
+    b = np.load(tmp_path / "b" / "feats.npy")
+    assert rows.dtype == np.float64 and len(rows) == 3 and np.all(np.diff(rows) > 0)
+    assert b.dtype == np.float32 and np.array_equal(b, x.float().numpy()[rows.astype(np.int64)])
+    assert b.nbytes + rows.nbytes <= 100
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "feats_rows.npy"))
+    assert np.array_equal(b, np.load(tmp_path / "c" / "feats.npy"))
+    # smallest first: the scalar is written whole, the rest of the budget goes to the large array
+    bench.dump_outputs(str(tmp_path / "d"), {"feats": x, "loss": torch.tensor(2.5)})
+    assert np.load(tmp_path / "d" / "loss.npy") == np.float32(2.5)
+    assert len(np.load(tmp_path / "d" / "feats_rows.npy")) == 3       # 96 bytes left: 3 rows of 24 + 3 indices
+    # one row alone over the budget: a seeded sample of the flattened elements
+    monkeypatch.setattr(bench, "DUMP_BYTES", 30)                      # a row needs 24 + 8; an element 4 + 8: 2 elements
+    bench.dump_outputs(str(tmp_path / "e"), {"feats": x})
+    rows = np.load(tmp_path / "e" / "feats_rows.npy")
+    e = np.load(tmp_path / "e" / "feats.npy")
+    assert e.shape == (2,) and np.array_equal(e, x.float().numpy().reshape(-1)[rows.astype(np.int64)])
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8)
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "f"), {"feats": x})
