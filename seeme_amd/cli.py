@@ -149,6 +149,10 @@ def _with_scene(cfg) -> bool:
     return "scene" in cfg.model.condition
 
 
+def _with_image(cfg) -> bool:
+    return "image" in cfg.model.condition
+
+
 # ----------------------------------------------------------------------------- train
 def train_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=None) -> Dict:
     args = build_parser("train").parse_args(argv)
@@ -197,8 +201,8 @@ def train_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=Non
             # strided shares (what the reference's DataLoader + DistributedSampler do, train.py:127-149); drop_last keeps the ranks in step
             batches = dm.iterate("train", B, shuffle=True, seed=int(cfg.SEED_VALUE), epoch=epoch, rank=rank, world=ws, drop_last=True)
         else:                           # synthetic stream: `iters_per_epoch` fresh batches
-            batches = (dm.batch(B, idx=(epoch * args.iters_per_epoch + it) * ws + rank, with_scene=_with_scene(cfg))
-                       for it in range(args.iters_per_epoch))
+            batches = (dm.batch(B, idx=(epoch * args.iters_per_epoch + it) * ws + rank, with_scene=_with_scene(cfg),
+                                with_image=_with_image(cfg)) for it in range(args.iters_per_epoch))
         n_it = 0
         for it, batch in enumerate(batches):
             loss = model.training_step(batch, it)
@@ -251,8 +255,8 @@ def test_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=None
             if hasattr(dm, "iterate"):  # files: ONE pass over the test split, every sequence exactly once over the ranks (test.py:115-133)
                 batches = dm.iterate("test", B, rank=rank, world=ws)
             else:
-                batches = (dm.batch(B, idx=10_000_000 + it * ws + rank, with_scene=_with_scene(cfg), split="test")
-                           for it in range(args.test_batches))
+                batches = (dm.batch(B, idx=10_000_000 + it * ws + rank, with_scene=_with_scene(cfg), split="test",
+                                    with_image=_with_image(cfg)) for it in range(args.test_batches))
             n_seq = 0
             for it, batch in enumerate(batches):
                 model.test_step(batch, it)

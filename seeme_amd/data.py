@@ -28,6 +28,11 @@ On-disk layout (what the reference reads; the datasets themselves are licence-ga
         (or from injected draws, for the tests).
     Optional <root>/interactee_pred_<split>.pkl {image name -> {"smpl_parameters": {global_orient, body_pose, betas}}}: EgoHMR
         estimates that replace the interactee's pose as the CONDITION (dataset.py:1215-1223, 1300-1321; translation stays the file's).
+    Image condition (``condition`` contains 'image'): <root>/image_feats_<split>.npz {names [F] image names as in
+        ``original_imgname``, feats [F,2048] float16 | float32}: the pooled ResNet-50 features of the frames (what
+        ``proscene.encode_image`` returns; the backbone runs outside this package).  As in the reference
+        (dataset.py:1657-1706) every access draws one frame of the sequence uniformly at random, in every split: on the device from
+        a seedable generator (or from injected draws).
 
 Files are read with loaders that execute nothing: ``np.load(allow_pickle=False)`` for arrays, and for the pickled ``.npy`` /
 ``.pkl`` containers an unpickler that only admits numpy array reconstruction and plain containers.
@@ -162,6 +167,32 @@ class EgoSequenceSplit:
         self.scene_table = self.scene_index = self.scene_xform = self.scene_flat = self.scene_off = self.scene_cnt = None
         if "scene" in self.condition:
             self._load_scenes(scene_root or root, first_image)
+        self.image_table = self.image_rows = self.image_off = self.image_cnt = None
+        if "image" in self.condition:
+            if pe:
+                raise NotImplementedError("POSE_ESTIMATION_TASK with an 'image' condition: the reference's image layouts carry no interactee "
+                                          "ground truth (dataset.py:1788-1792)")
+            self._load_image_feats(os.path.join(root, f"image_feats_{split}.npz"))
+
+    def _load_image_feats(self, path: str):
+        """The feature table of the split and, per sequence, the table rows of its frames (flat, with offsets and counts)."""
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"'image' condition: {path} (names [F], feats [F,2048]) is missing; see INTEGRATION.md")
+        with np.load(path, allow_pickle=False) as z:
+            names, feats = [str(n) for n in z["names"]], z["feats"]
+        if feats.ndim != 2 or feats.shape[0] != len(names) or feats.dtype not in (np.float16, np.float32):
+            raise ValueError(f"{path}: feats is {feats.shape} {feats.dtype}, names {len(names)}: expected float16 / float32 [F,2048], one row per name")
+        row = {n: i for i, n in enumerate(names)}
+        missing = [im for ims in self.images for im in ims if im not in row]
+        if missing:
+            raise KeyError(f"{path} lacks the features of {len(missing)} frame(s) of split '{self.split}', e.g. {missing[:5]}")
+        cnt = np.array([len(ims) for ims in self.images], np.int64)
+        if (cnt == 0).any():
+            raise ValueError(f"split '{self.split}': a sequence without frames cannot draw an image")
+        self.image_table = torch.from_numpy(np.ascontiguousarray(feats))                              # [F,2048], the file's dtype
+        self.image_rows = torch.from_numpy(np.array([row[im] for ims in self.images for im in ims], np.int64))
+        self.image_cnt = torch.from_numpy(cnt)
+        self.image_off = torch.from_numpy(np.concatenate([[0], np.cumsum(cnt)[:-1]]).astype(np.int64))
 
     def _load_scenes(self, scene_root: str, first_image: List[str]):
         N = len(first_image)
@@ -209,7 +240,7 @@ class EgoSequenceSplit:
 
     def to(self, device, pinned: bool = False):
         for k in ("motion", "transl", "beta", "utils", "length", "scene_table", "scene_index", "scene_xform", "scene_flat", "scene_off",
-                  "scene_cnt", "pe_motion", "pe_beta"):
+                  "scene_cnt", "pe_motion", "pe_beta", "image_table", "image_rows", "image_off", "image_cnt"):
             t = getattr(self, k)
             if t is not None:
                 setattr(self, k, t.pin_memory() if pinned else t.to(device))
@@ -218,6 +249,20 @@ class EgoSequenceSplit:
     @property
     def has_scene(self) -> bool:
         return self.scene_table is not None or self.scene_flat is not None
+
+    @property
+    def has_image(self) -> bool:
+        return self.image_table is not None
+
+    def image_feats(self, index: torch.Tensor, generator: Optional[torch.Generator] = None, draws=None) -> torch.Tensor:
+        """[B,2048] float32: the features of ONE frame per item, drawn uniformly from the item's frames on every access
+        (``np.random.randint(0, number_of_images)``, dataset.py:1657-1660; here floor(u n) from `generator` on the device).
+        `draws` = u [B] in [0,1) injects the random numbers."""
+        dev = self.image_table.device
+        cnt, off = self.image_cnt.index_select(0, index), self.image_off.index_select(0, index)
+        u = draws.to(dev) if draws is not None else torch.rand(index.shape[0], device=dev, generator=generator)
+        pick = torch.minimum((u.double() * cnt.double()).long(), cnt - 1) + off
+        return self.image_table.index_select(0, self.image_rows.index_select(0, pick)).float()
 
     def scenes(self, index: torch.Tensor, generator: Optional[torch.Generator] = None, draws=None) -> torch.Tensor:
         """The scene clouds of a batch of items, in the frame the reference hands to the model.
@@ -248,6 +293,9 @@ class EgoSequenceSplit:
         out = [self.motion[i], self.transl[i], self.beta[i], self.utils[i]]
         if self.has_scene:
             out.append(self.scenes(ix)[0])
+        if self.has_image:                       # image layouts: (..., [scene], images, length), dataset.py:1788-1792
+            out += [self.image_feats(ix)[0], self.length[i]]
+            return tuple(out)
         out.append(self.length[i])
         if self.pose_estimation_task:            # (motion_interacte_pe_gt, interactee_transl_pe_gt, interactee_beta_pe_gt), :1765-1781
             out += [self.pe_motion[i], self.transl[i, 1:2], self.pe_beta[i]]
@@ -286,8 +334,9 @@ class EgoDataModule:
         self.mean = torch.from_numpy(any_split.mean).to(self.device)
         self.std = torch.from_numpy(any_split.std).to(self.device)
         self.with_scene = any_split.has_scene
+        self.with_image = any_split.has_image
         self.pose_estimation_task = pose_estimation_task
-        self.generator = torch.Generator(device=self.device if storage == "device" else "cpu").manual_seed(int(seed))   # scene sampling / jitter
+        self.generator = torch.Generator(device=self.device if storage == "device" else "cpu").manual_seed(int(seed))   # scene / frame draws
 
     def renorm(self, features):
         """features * std[0, :numdims] + mean[0, :numdims]  (EgoBody.py:151-157, Gimo.py:139-145).  For GIMO the translation
@@ -297,21 +346,24 @@ class EgoDataModule:
             return G.renorm(features, self.mean[:, idx].contiguous(), self.std[:, idx].contiguous())
         return G.renorm(features, self.mean, self.std)
 
-    def collate(self, split: str, index: torch.Tensor):
+    def collate(self, split: str, index: torch.Tensor, image_draws=None):
         """default_collate of the reference's items, from the resident tensors: (motion [B,T,2,P], transl [B,2,T,3],
-        beta [B,2,T,10], utils [B,T,6], [scene [B,P,3]], length [B,1], [image names])."""
+        beta [B,2,T,10], utils [B,T,6], [scene [B,P,3]], length [B,1], [image names]); with the image condition
+        (motion, transl, beta, utils, [scene], images [B,2048], length).  image_draws: u [B] of the frame draw (tests)."""
         s = self.splits[split]
         ix = index.to(s.motion.device)
         sel = lambda t: t.index_select(0, ix)
         out = [sel(s.motion), sel(s.transl), sel(s.beta), sel(s.utils)]
         if s.has_scene:
             out.append(s.scenes(ix, generator=self.generator))
+        if s.has_image:
+            out.append(s.image_feats(ix, generator=self.generator, draws=image_draws))
         out.append(sel(s.length))
         if self.pose_estimation_task:            # the interactee's ground truth closes the tuple (dataset.py:1765-1781; MLD.ego_eval batch[-3:])
             out += [sel(s.pe_motion), sel(s.transl)[:, 1:2].contiguous(), sel(s.pe_beta)]
         if self.storage == "pinned":
             out = [t.pin_memory().to(self.device, non_blocking=True) for t in out]
-        if s.has_scene and not self.pose_estimation_task:
+        if s.has_scene and not s.has_image and not self.pose_estimation_task:
             out.append([s.images[int(i)] for i in index.tolist()])
         return tuple(out)
 
@@ -328,7 +380,7 @@ class EgoDataModule:
                 break
             yield self.collate(split, ix)
 
-    def batch(self, B, idx=0, with_scene=None, lengths=None, pose_estimation=False, split: str = "train"):
+    def batch(self, B, idx=0, with_scene=None, lengths=None, pose_estimation=False, split: str = "train", with_image=None):
         """Batch number `idx` of an endless shuffled stream over `split` (the interface seeme_amd.cli trains / tests on)."""
         sp = split if split in self.splits else next(iter(self.splits))
         n = len(self.splits[sp])

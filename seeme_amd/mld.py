@@ -19,7 +19,10 @@ What runs where
   * Only the live flows are implemented; the reference's dead code (``forward`` calling the undefined
     ``feats2joints``, t2m_eval, the ``save_for_edo`` debug dump -- SURVEY.md App. D) is not reproduced:
     ``forward``/``sample`` = what ``ego_eval`` really does (condition -> reverse diffusion -> decode).
-  * Deliberate, documented deviations from the reference: none by default.  ``TEST.SAMPLE_MEAN``
+  * The image condition takes the ResNet-50 backbone's pooled features [B,2048] in the batch's image slot (the backbone is out of
+    scope); ``output_images`` is trainable and its stage-2 forward / gradient are glue problems, evaluation projects with a torch op.
+  * Deliberate, documented deviations from the reference: none by default, except where the reference cannot
+    run as written (the image branches of ``ego_eval``: batch layout, guidance).  ``TEST.SAMPLE_MEAN``
     (condition on the posterior mean instead of a sample) and ``TEST.CFG_SCENE_ORDER: fixed`` (classifier-free guidance
     with the unconditional scene token in the unconditional half) are opt-in.
 """
@@ -37,6 +40,23 @@ from .config import instantiate_from_config
 from .denoiser_autograd import denoiser_forward_torch
 from .respointnet import ResnetPointnet
 from .smpl import SMPL
+
+
+IMAGE_FEAT_DIM = 2048          # pooled ResNet-50 feature of proscene.encode_image (prohmr_scene.py:99-100, BACKBONE.OUT_CHANNELS)
+
+
+def split_batch(condition, batch):
+    """The dataset's tuple by condition (dataset.py:1754-1794): (motion, transl, beta, utils, scene | None, images | None, length,
+    rest).  image + scene: (..., scene, images, length); image only: (..., images, length); scene only: (..., scene, length,
+    names | interactee ground truth); neither: (..., length)."""
+    motion, transl, beta, utils_ = batch[:4]
+    k = 4
+    scene = images = None
+    if "scene" in condition:
+        scene, k = batch[k], k + 1
+    if "image" in condition:
+        images, k = batch[k], k + 1
+    return motion, transl, beta, utils_, scene, images, batch[k], tuple(batch[k + 1:])
 
 
 # ----------------------------------------------------------------------------- losses / metrics
@@ -222,7 +242,9 @@ class SyntheticEgoDataModule:
     def renorm(self, features):
         return G.renorm(features, self.mean, self.std)
 
-    def batch(self, B, idx=0, with_scene=False, lengths=None, pose_estimation=False, split="train"):
+    def batch(self, B, idx=0, with_scene=False, lengths=None, pose_estimation=False, split="train", with_image=False):
+        """with_image: pooled image features [B,2048] (non-negative, as after the backbone's final ReLU + pooling) in the image
+        layouts (motion, transl, beta, utils, [scene], images, length)."""
         g = torch.Generator().manual_seed(self.seed * 7919 + idx)
         T = self.T
         motion = 0.5 * torch.randn(B, T, 2, self.pose_dim, generator=g)
@@ -234,6 +256,14 @@ class SyntheticEgoDataModule:
         out = [motion.to(dev), transl.to(dev), beta.to(dev), utils_.to(dev)]
         if with_scene:
             out.append((torch.rand(B, self.n_points, 3, generator=g) * 6 - 3).to(dev))
+        if with_image:
+            if pose_estimation:
+                raise NotImplementedError("the image layouts carry no interactee ground truth (dataset.py:1788-1792)")
+            # (a generator of its own: the other tensors stay those of the same idx without images)
+            gi = torch.Generator().manual_seed(self.seed * 7919 + idx + 104729)
+            out.append(torch.rand(B, IMAGE_FEAT_DIM, generator=gi).pow(2).to(dev))
+            out.append(length.to(dev))
+            return tuple(out)
         out.append(length.to(dev))
         if with_scene and not pose_estimation:
             out.append([])          # img_path / dict_images slot
@@ -290,8 +320,9 @@ class MLD(nn.Module):
             self.nfeats = 69 if self.predict_transl else 66
         else:
             self.nfeats = cfg.model.nfeats
-        if "image" in self.condition:
-            raise NotImplementedError("image conditioning (ProHMR ResNet-50 backbone) is outside the accelerated path")
+        if "image" in self.condition and self.pose_estimation_task:
+            raise NotImplementedError("TEST.POSE_ESTIMATION_TASK with an 'image' condition: the reference's dataset returns no interactee "
+                                      "ground truth in the image batch layouts (dataset.py:1788-1792)")
 
         # SMPL (mld.py:151-153); frozen
         if smpl_model is not None:
@@ -303,6 +334,9 @@ class MLD(nn.Module):
 
         self.vae_type = cfg.model.get("vae_type", None) or \
             cfg.model.motion_vae.target.split(".")[-1].lower().replace("vae", "")      # mld.py:174-179
+        if "image" in self.condition:                                     # mld.py:251-255; trainable in stage 2
+            # the ResNet-50 backbone (proscene.encode_image) stays outside: batches carry its pooled [B,2048] features
+            self.output_images = nn.Sequential(nn.ReLU(), nn.Linear(IMAGE_FEAT_DIM, 256))
         if "scene" in self.condition:                                     # mld.py:182-207, 257-261
             self.proscene = _SceneEncoderHolder()
             for p in self.proscene.parameters():
@@ -371,6 +405,22 @@ class MLD(nn.Module):
             return s512
         # output_scene = ReLU + Linear(512,256) (trainable, mld.py:257-261): torch op so that autograd sees it
         return self.output_scene(s512).unsqueeze(0)                       # [1,B,256]
+
+    @staticmethod
+    def _image_feats(images) -> torch.Tensor:
+        """The image slot of a batch: pooled backbone features [B,2048] (what proscene.encode_image returns, mld.py:895-896)."""
+        if not torch.is_tensor(images):
+            raise TypeError(f"the image slot of the batch holds {type(images).__name__}: expected pooled image features [B,{IMAGE_FEAT_DIM}]")
+        if images.dim() == 4:
+            raise NotImplementedError(f"the image slot holds images {tuple(images.shape)}: the ResNet-50 backbone (proscene.encode_image) "
+                                      f"is outside this path -- pass its pooled features [B,{IMAGE_FEAT_DIM}] (INTEGRATION.md)")
+        if images.dim() != 2 or images.shape[1] != IMAGE_FEAT_DIM or not images.is_floating_point():
+            raise ValueError(f"image features are {tuple(images.shape)} {images.dtype}: expected float [B,{IMAGE_FEAT_DIM}]")
+        return images.float()
+
+    def _image_token(self, images) -> torch.Tensor:
+        # output_images = ReLU + Linear(2048,256) (trainable, mld.py:251-255): torch op, as output_scene above
+        return self.output_images(self._image_feats(images)).unsqueeze(0)   # [1,B,256]
 
     def _wearer_features(self, feats_ref, transl, idx):
         f = feats_ref[:, :, idx, :]
@@ -448,19 +498,22 @@ class MLD(nn.Module):
         eps = (target rsample noise, condition rsample noise) [1,B,256] each, then `noise` and `timesteps` (:591-601)."""
         m_scene, m_int = masks if masks is not None else (None, None)
         e_z, e_c = eps if eps is not None else (None, None)
-        if "scene" in self.condition:
-            feats_ref, transl, beta, utils_, scene, length = batch[:6]
-            scene = self._scene_token(scene, cfg_mask_train=True, mask=m_scene, code_only=True)      # [B,512] PointNet code
-        else:
-            feats_ref, transl, beta, utils_, length = batch[:5]
-            scene = None
+        feats_ref, transl, beta, utils_, scene, images, length, _ = split_batch(self.condition, batch)
+        if images is not None:
+            images = self._image_feats(images)                                # [B,2048] (no input mask: mld.py:889-909)
+        if scene is not None:
+            # the classifier-free input mask of the scene exists only without an image (mld.py:889-922)
+            scene = self._scene_token(scene, cfg_mask_train=images is None, mask=m_scene, code_only=True)      # [B,512] PointNet code
         feats_ref, transl = feats_ref.float(), transl.float()
         lengths = [feats_ref.shape[1]] * feats_ref.shape[0]
-        glue = self._stage2_glue(int(scene is not None) + int("interactee" in self.condition)) if feats_ref.is_cuda else None
+        n_tok = int(scene is not None) + int(images is not None) + int("interactee" in self.condition)
+        glue = self._stage2_glue(n_tok) if feats_ref.is_cuda else None
         if glue is not None:
-            return self._train_diffusion_forward_glue(glue, feats_ref, transl, scene, lengths, noise, timesteps, e_z, e_c, m_int)
+            return self._train_diffusion_forward_glue(glue, feats_ref, transl, scene, lengths, noise, timesteps, e_z, e_c, m_int, images)
         if scene is not None:
             scene = self.output_scene(scene).unsqueeze(0)                     # [1,B,256]
+        if images is not None:
+            images = self.output_images(images).unsqueeze(0)                  # [1,B,256]
         with torch.no_grad():
             idx = 0 if self.estimate == "wearer" else 1
             f_tgt = self._wearer_features(feats_ref, transl, idx)
@@ -484,14 +537,10 @@ class MLD(nn.Module):
                 z_cond = mu[:, B:] + eps_c * std[:, B:]
             else:
                 z, _ = self._sample_latent(f_tgt, lengths, e_z)
-        if scene is not None and z_cond is not None:
-            cond_emb = torch.cat([z_cond, scene], dim=0)                    # :991-993
-        elif scene is not None:
-            cond_emb = scene
-        elif z_cond is not None:
-            cond_emb = z_cond
-        else:
+        toks = [t for t in (z_cond, scene, images) if t is not None]      # :991-1013: [z_cond, scene, images] in this order
+        if not toks:
             raise ValueError("no condition: MldDenoiser needs at least one condition token")
+        cond_emb = torch.cat(toks, dim=0) if len(toks) > 1 else toks[0]
         return {**self._diffusion_process(z, cond_emb, lengths, noise=noise, timesteps=timesteps)}
 
     def _vae_trainer(self, T: int):
@@ -522,7 +571,7 @@ class MLD(nn.Module):
             object.__setattr__(self, "_glue", g)
         return g
 
-    def _train_diffusion_forward_glue(self, glue, feats_ref, transl, s512, lengths, noise, timesteps, e_z, e_c, m_int):
+    def _train_diffusion_forward_glue(self, glue, feats_ref, transl, s512, lengths, noise, timesteps, e_z, e_c, m_int, img=None):
         """train_diffusion_forward + _diffusion_process with everything between the frozen encoders and the loss in
         stage2_glue's kernels; the random draws keep the reference's order (mld.py:917-919,944-984,591-601)."""
         with torch.no_grad():
@@ -544,7 +593,7 @@ class MLD(nn.Module):
             noise = torch.randn(B, 1, 256, device=dev) if noise is None else noise.to(f_tgt)
             if timesteps is None:
                 timesteps = torch.randint(0, self.noise_scheduler.config.num_train_timesteps, (B,), device=dev)
-        noise_pred, latents = glue(dist, eps_z, eps_c, noise, timesteps.long(), s512)
+        noise_pred, latents = glue(dist, eps_z, eps_c, noise, timesteps.long(), s512, img)
         n_set = {"noise": noise.reshape(B, 1, 256), "noise_prior": 0, "noise_pred": noise_pred, "noise_pred_prior": 0}
         if not self.predict_epsilon:
             n_set["pred"] = noise_pred
@@ -647,19 +696,24 @@ class MLD(nn.Module):
         if self.pose_estimation_task:       # batch ends with the interactee's ground truth (mld.py:1119-1131)
             batch, int_gt = tuple(batch[:-3]), tuple(t.float() for t in batch[-3:])
         eps_c, eps_u = cond_noise if isinstance(cond_noise, (tuple, list)) else (cond_noise, None)
-        if "scene" in self.condition:
-            feats_ref, transl, beta, utils_, scene, length = batch[:6]
-            scene_tok = None
-            if self.stage != "vae":
+        # image layouts: `length` last, as the dataset hands it over (the reference's unpack at :1079 / :1093 omits it: DESIGN 6a)
+        feats_ref, transl, beta, utils_, scene, images, length, _ = split_batch(self.condition, batch)
+        scene_tok = img_tok = None
+        if images is not None and self.stage != "vae":
+            if self.do_classifier_free_guidance:
+                raise NotImplementedError("ego_eval with an 'image' condition and guidance_scale > 1: the reference builds no unconditional "
+                                          "scene / image token in the image branches (mld.py:1076-1100) while _diffusion_reverse halves the "
+                                          "batch (:437-438), so that configuration cannot run; training with it is defined (DESIGN 6a)")
+            img_tok = self._image_token(images)                           # (no unconditional image token: see above)
+            if scene is not None:
                 scene_tok = self._scene_token(scene)
-                if self.do_classifier_free_guidance:                       # zero-scene branch (:1144-1158)
-                    unc = self._scene_token(torch.zeros_like(scene))
-                    # the reference concatenates [scene, scene_uncond] while _diffusion_reverse takes the FIRST half as
-                    # unconditional (:489): reproduced by default, TEST.CFG_SCENE_ORDER 'fixed' puts uncond first
-                    scene_tok = torch.cat([scene_tok, unc] if self.cfg_scene_order == "reference" else [unc, scene_tok], dim=1)
-        else:
-            feats_ref, transl, beta, utils_, length = batch[:5]
-            scene_tok = None
+        elif scene is not None and self.stage != "vae":
+            scene_tok = self._scene_token(scene)
+            if self.do_classifier_free_guidance:                           # zero-scene branch (:1144-1158)
+                unc = self._scene_token(torch.zeros_like(scene))
+                # the reference concatenates [scene, scene_uncond] while _diffusion_reverse takes the FIRST half as
+                # unconditional (:489): reproduced by default, TEST.CFG_SCENE_ORDER 'fixed' puts uncond first
+                scene_tok = torch.cat([scene_tok, unc] if self.cfg_scene_order == "reference" else [unc, scene_tok], dim=1)
         feats_ref, transl, beta = feats_ref.float(), transl.float(), beta.float()
         lengths = length.long().reshape(-1).tolist()
         idx_ref = 0 if self.estimate == "wearer" else 1
@@ -672,7 +726,7 @@ class MLD(nn.Module):
                 if self.do_classifier_free_guidance:
                     unc, _ = self._sample_latent(torch.zeros_like(f_int), lengths, eps_u, mean=self.sample_mean)
                     text_emb = torch.cat([unc, text_emb], dim=1)
-            toks = [t for t in (text_emb, scene_tok) if t is not None]
+            toks = [t for t in (text_emb, scene_tok, img_tok) if t is not None]      # :1297-1306: [text, scene, images]
             if not toks:
                 raise ValueError("no condition tokens")
             cond_emb = torch.cat(toks, dim=0)                               # [N, B or 2B, 256]

@@ -2,12 +2,12 @@
 
 What ``MLD.train_diffusion_forward`` / ``_diffusion_process`` (mld/models/modeltype/mld.py:582-631,887-1017) do between the
 frozen encoders and the loss -- posterior rsample, ``scheduler.add_noise``, timestep features + TimestepEmbedding MLP,
-``output_scene``, ``MldDenoiser.forward``'s condition / time tables, the token-0 chain -- runs here as
+``output_scene``, ``output_images``, ``MldDenoiser.forward``'s condition / time tables, the token-0 chain -- runs here as
 
-    forward : k_glue_rows -> k_gg (time MLP layer 1, output_scene) -> k_glue_ln -> k_gg (time MLP layer 2)
+    forward : k_glue_rows -> k_gg (time MLP layer 1, output_scene, output_images) -> k_glue_ln -> k_gg (time MLP layer 2)
               -> k_gg (all tables) -> k_den_sample (chain, intermediates saved)
     backward: k_den_bwd -> seeme_den_wgrad (chain weights) -> k_gg (data gradients of the tables) -> k_glue_mid
-              -> k_gg (time MLP) -> k_gg (every weight / bias gradient of the tables, time MLP and output_scene)
+              -> k_gg (time MLP) -> k_gg (every weight / bias gradient of the tables, time MLP, output_scene and output_images)
 
 with every parameter gradient accumulated straight into ``.grad`` (the views of ``distributed.GradBucket`` once it exists; the
 weight-gradient descriptor table is rebuilt when those tensors move, so keep them -- ``MLD.optimizer_step`` does):
@@ -87,13 +87,14 @@ def _wgrad(srcs, g, Nout, Kin, gbias, **kw):
 class _Plan:
     """Buffers and descriptor tables for one (B, token layout)."""
 
-    def __init__(self, glue: "Stage2Glue", B: int, has_int: bool, has_scene: bool):
+    def __init__(self, glue: "Stage2Glue", B: int, has_int: bool, has_scene: bool, has_img: bool = False):
         den, dev = glue.den, glue.dev
-        self.B, self.has_int, self.has_scene = B, has_int, has_scene
-        N = int(has_int) + int(has_scene)
+        self.B, self.has_int, self.has_scene, self.has_img = B, has_int, has_scene, has_img
+        N = int(has_int) + int(has_scene) + int(has_img)
         self.N, self.M = N, B * N
         M = self.M
-        self.slot_c, self.slot_s = 0, int(has_int)
+        # token slots in the reference's order [interactee, scene, image] (mld.py:991-1013)
+        self.slot_c, self.slot_s, self.slot_i = 0, int(has_int), int(has_int) + int(has_scene)
         lay = glue.pack.lay
         z = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
         self.cond, self.tfeat, self.pre1, self.emb = z(B, N, 256), z(B, 256), z(B, 256), z(B, 256)
@@ -101,6 +102,7 @@ class _Plan:
         self.xhat, self.rstd = z(M, 256), z(M)
         self.ctab, self.ttab = z(B, N, 5120), z(B, 7680)
         self.s512 = z(B, 512) if has_scene else None
+        self.img = z(B, glue.img_dim) if has_img else None
         self.save = z(B, lay["DT_TOTAL"])
         self.trow = torch.arange(B, device=dev, dtype=torch.int32)
         self.gout = z(B, lay["DB_TOTAL"])
@@ -121,6 +123,10 @@ class _Plan:
             lin = glue.output_scene[1]
             l0.append(_fwd(P(self.s512), 512, P(lin.weight), 512, P(lin.bias), P(self.cond) + 4 * 256 * self.slot_s, N * 256, B, 256,
                            a_pro=2))
+        if has_img:                       # output_images = ReLU + Linear(2048, 256), the same prologue
+            lin = glue.output_images[1]
+            K = glue.img_dim
+            l0.append(_fwd(P(self.img), K, P(lin.weight), K, P(lin.bias), P(self.cond) + 4 * 256 * self.slot_i, N * 256, B, 256, a_pro=2))
         self.g_l0 = _Group(l0, dev)
         self.g_l1 = _Group([_fwd(P(self.pre1), 256, P(te.linear_2.weight), 256, P(te.linear_2.bias), P(self.emb), 256, B, 256, a_pro=1)], dev)
         l2 = []
@@ -184,6 +190,10 @@ class _Plan:
             lin = glue.output_scene[1]
             b3.append(_wgrad([(P(self.dcond) + 4 * 256 * self.slot_s, N * 256, P(self.s512), 512, B)], G(lin.weight), 256, 512, G(lin.bias),
                              b_pro=2))
+        if self.has_img:
+            lin = glue.output_images[1]
+            b3.append(_wgrad([(P(self.dcond) + 4 * 256 * self.slot_i, N * 256, P(self.img), glue.img_dim, B)], G(lin.weight), 256, glue.img_dim,
+                             G(lin.bias), b_pro=2))
         self.g_b3 = _Group(b3, glue.dev)
         mid.M, mid.B = M, B
         mid.dxl, mid.dcs, mid.xhat, mid.rstd, mid.dcond = P(self.dxl), P(self.dcs), P(self.xhat), P(self.rstd), P(self.dcond)
@@ -193,8 +203,8 @@ class _Plan:
 
 class _Stage2(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, glue, hook, dist, eps_z, eps_c, noise, timesteps, s512):
-        plan = glue._forward(dist, eps_z, eps_c, noise, timesteps, s512)
+    def forward(ctx, glue, hook, dist, eps_z, eps_c, noise, timesteps, s512, img):
+        plan = glue._forward(dist, eps_z, eps_c, noise, timesteps, s512, img)
         ctx.glue, ctx.plan = glue, plan
         out, latents = plan.out, plan.latents
         ctx.mark_non_differentiable(latents)
@@ -203,17 +213,19 @@ class _Stage2(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, _dlat):
         ctx.glue._backward(ctx.plan, dout)
-        return (None,) * 8
+        return (None,) * 9
 
 
 class Stage2Glue:
-    """Owner of the plans of one MLD model (denoiser + optional output_scene + noise scheduler)."""
+    """Owner of the plans of one MLD model (denoiser + optional output_scene / output_images + noise scheduler)."""
 
     def __init__(self, mld):
         den = mld.denoiser
         self.den = den
         self.dev = den.query_pos.pe.device
         self.output_scene = getattr(mld, "output_scene", None)
+        self.output_images = getattr(mld, "output_images", None)
+        self.img_dim = self.output_images[1].in_features if self.output_images is not None else 0
         self.scheduler = mld.noise_scheduler
         self.acp = self.scheduler.alphas_cumprod.to(self.dev, torch.float32).contiguous()
         half = den.text_encoded_dim // 2
@@ -232,6 +244,8 @@ class Stage2Glue:
                    b.ffn.proj_out.emb_layers[1].weight, b.ffn.proj_out.emb_layers[1].bias]
         if self.output_scene is not None:
             ps += [self.output_scene[1].weight, self.output_scene[1].bias]
+        if self.output_images is not None:
+            ps += [self.output_images[1].weight, self.output_images[1].bias]
         self.params = ps
         self._param_key = tuple(p.data_ptr() for p in ps)
 
@@ -248,28 +262,34 @@ class Stage2Glue:
         den = mld.denoiser
         if not hip_train_supported(den, n_tokens) or den.text_encoded_dim != 256:
             return False
-        ps = list(den.parameters()) + (list(mld.output_scene.parameters()) if getattr(mld, "output_scene", None) is not None else [])
+        ps = list(den.parameters())
+        for name in ("output_scene", "output_images"):
+            if getattr(mld, name, None) is not None:
+                ps += list(getattr(mld, name).parameters())
         return all(p.requires_grad and p.dtype == torch.float32 for p in ps)
 
     def stale(self) -> bool:
         return tuple(p.data_ptr() for p in self.params) != self._param_key
 
-    def __call__(self, dist, eps_z, eps_c, noise, timesteps, s512):
+    def __call__(self, dist, eps_z, eps_c, noise, timesteps, s512, img=None):
         """dist [2,R,256] (R = B, or 2B with the condition motion in rows B..); eps_z / eps_c / noise [B,256]-shaped; timesteps
-        [B] int64; s512 [B,512] PointNet code or None.  Returns (noise_pred [B,1,256] differentiable, latents [B,1,256])."""
-        out, lat = _Stage2.apply(self, self.params[0], dist, eps_z, eps_c, noise, timesteps, s512)
+        [B] int64; s512 [B,512] PointNet code or None; img [B,2048] pooled image features or None.  Returns (noise_pred [B,1,256]
+        differentiable, latents [B,1,256])."""
+        out, lat = _Stage2.apply(self, self.params[0], dist, eps_z, eps_c, noise, timesteps, s512, img)
         B = out.shape[0]
         return out.view(B, 1, 256), lat.view(B, 1, 256)
 
     # ------------------------------------------------------------------ forward / backward bodies
-    def _forward(self, dist, eps_z, eps_c, noise, timesteps, s512) -> _Plan:
+    def _forward(self, dist, eps_z, eps_c, noise, timesteps, s512, img=None) -> _Plan:
         self._pack()
         B = noise.reshape(-1, 256).shape[0]
-        has_int, has_scene = eps_c is not None, s512 is not None
-        key = (B, has_int, has_scene)
+        has_int, has_scene, has_img = eps_c is not None, s512 is not None, img is not None
+        if has_img and self.output_images is None:
+            raise ValueError("image features given to a model without output_images")
+        key = (B, has_int, has_scene, has_img)
         plan = self.plans.get(key)
         if plan is None or plan.busy:        # busy: a second forward before the first one's backward (keep its saved tensors intact)
-            plan = _Plan(self, B, has_int, has_scene)
+            plan = _Plan(self, B, has_int, has_scene, has_img)
             self.plans[key] = plan
         dev = self.dev
         st = L.current_stream()
@@ -284,6 +304,10 @@ class Stage2Glue:
         plan.latents = torch.empty(B, 256, device=dev, dtype=torch.float32)
         if has_scene:
             plan.s512.copy_(s512.reshape(B, 512))
+        if has_img:
+            if img.shape != (B, self.img_dim):
+                raise ValueError(f"image features are {tuple(img.shape)}: expected [{B}, {self.img_dim}]")
+            plan.img.copy_(img)
         a = L.GlueRows()
         a.B, a.N, a.dist, a.dist_rows, a.eps_z = B, plan.N, dist.data_ptr(), dist.shape[1], eps_z.data_ptr()
         if has_int:
