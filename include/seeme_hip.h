@@ -515,6 +515,17 @@ int seeme_vt_dropout(const float* x, const unsigned char* mask, float scale, flo
 int seeme_vt_cross_rows(const float* cvn, const float* bo, const unsigned char* wmask, const unsigned char* m2, float scale,
                         int B, int S, float* out, void* stream);
 
+/* ------------------------------------------------------------------ K hypotheses per sequence: errors and diversity
+ * jts_pred [B*K,T,24,3] (row b*K + k = hypothesis k of sequence b), jts_ref [B,T,24,3], fp32 metres, 16-byte aligned; lengths [B].
+ * per_hyp [3,B,K] = MPJPE, ROOT_ERROR, ACCL of EgoMetrics.per_sequence for hypothesis k against the reference of b (mm);
+ * per_seq [2,B] = APD_JOINTS (EgoHMR form, test_egohmr.py:519-520: half the mean distance over unordered pairs) and STD_JOINTS
+ * (unbiased standard deviation over K of every joint coordinate, :496), means over the valid frames (mm); both 0 for K = 1.
+ * K <= 32; every length must be in 1..T (as per_sequence, the sums run over min(len, T) frames and are divided by len, so a length
+ * outside that range gives a meaningless or non-finite row; it is never read out of bounds).  No atomics: bitwise reproducible.  The workspace holds the per-chunk partial sums. */
+size_t seeme_hyp_metrics_workspace_bytes(int B, int K, int T);
+int seeme_hyp_metrics(const float* jts_pred, const float* jts_ref, const int32_t* lengths, int B, int K, int T,
+                      float* per_hyp, float* per_seq, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -192,6 +192,8 @@ _SIGNATURES = {
                                              C.c_size_t, fp]),
     "seeme_smpl_workspace_bytes": (C.c_size_t, [C.c_int]),
     "seeme_smpl_lbs": (C.c_int, [C.POINTER(SmplModel), fp, fp, C.c_int, fp, C.c_int, fp, fp, fp, C.c_size_t, fp]),
+    "seeme_hyp_metrics_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "seeme_hyp_metrics": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, C.c_int, fp, fp, fp, C.c_size_t, fp]),
 }
 
 _lib: Optional[C.CDLL] = None

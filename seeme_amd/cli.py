@@ -53,6 +53,7 @@ def build_parser(phase: str) -> argparse.ArgumentParser:
     s.add_argument("--frames", type=int, default=196)
     s.add_argument("--folder", type=str, default=None, help="override FOLDER (experiment root)")
     s.add_argument("--checkpoint", type=str, default=None, help="override TEST.CHECKPOINTS")
+    s.add_argument("--num_hypotheses", type=int, default=None, help="override TEST.NUM_HYPOTHESES (draws per sequence, 1..32)")
     return p
 
 
@@ -62,6 +63,8 @@ def load_cfg(args, phase: str):
         cfg.DEBUG = (not args.nodebug) if args.nodebug else cfg.get("DEBUG", False)
         if cfg.DEBUG:
             cfg.NAME = "debug--" + str(cfg.get("NAME", "exp"))       # mld/config.py:190-193
+    if getattr(args, "num_hypotheses", None) is not None:
+        cfg.TEST.NUM_HYPOTHESES = args.num_hypotheses
     if args.folder:
         cfg.FOLDER = args.folder
     cfg.setdefault("FOLDER", "./experiments")
@@ -250,6 +253,7 @@ def test_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=None
     all_metrics: Dict[str, List[float]] = {}
     for rep in range(int(cfg.TEST.REPLICATION_TIMES)):
         model.EgoMetric.reset()
+        model.HypMetric.reset()
         t0 = time.perf_counter()
         with torch.no_grad():
             if hasattr(dm, "iterate"):  # files: ONE pass over the test split, every sequence exactly once over the ranks (test.py:115-133)
@@ -266,6 +270,9 @@ def test_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=None
         sums = D.reduce_sums(model.EgoMetric.sums().to(dev)).cpu()
         metrics = model.EgoMetric.compute(sums)
         metrics["seqs_per_s"] = ws * n_seq / dt
+        if model.num_hypotheses > 1:    # K draws per sequence in this pass: best-of-K / mean-of-K error and the diversity of the draws
+            metrics.update(model.HypMetric.compute(D.reduce_sums(model.HypMetric.sums().to(dev)).cpu(), model.num_hypotheses))
+            metrics["samples_per_s"] = model.num_hypotheses * metrics["seqs_per_s"]
         log.info("Replication %d: %s", rep, json.dumps({k: round(v, 4) for k, v in metrics.items()}))
         for k, v in metrics.items():
             all_metrics.setdefault(k, []).append(float(v))

@@ -38,6 +38,7 @@ import torch.nn as nn
 from . import geometry as G
 from .config import instantiate_from_config
 from .denoiser_autograd import denoiser_forward_torch
+from .hyp_metrics import K_MAX, HypothesisMetrics, best_index, hyp_metrics_hip, keep_mask
 from .respointnet import ResnetPointnet
 from .smpl import SMPL
 
@@ -180,13 +181,19 @@ class EgoMetrics:
         else:
             out["ACCL"] = torch.zeros(B, device=dev, dtype=ref.dtype)
         if quat_pred is not None and quat_ref is not None:
-            Rg = EgoMetrics.quat_to_rotmat(quat_ref.reshape(-1, 4).to(ref.dtype))
-            Rp = EgoMetrics.quat_to_rotmat(quat_pred.reshape(-1, 4).to(ref.dtype))
-            err = (torch.eye(3, device=dev, dtype=ref.dtype) - Rg @ torch.linalg.inv(Rp)).flatten(1).norm(dim=1).reshape(B, T)
-            out["HEAD_ORIENTATION_ERROR"] = (err * mask).sum(1) / lens
+            out["HEAD_ORIENTATION_ERROR"] = EgoMetrics.head_orientation_error(quat_pred, quat_ref, mask, lens)
         else:
             out["HEAD_ORIENTATION_ERROR"] = torch.zeros(B, device=dev, dtype=ref.dtype)
         return out
+
+    @staticmethod
+    def head_orientation_error(quat_pred, quat_ref, mask, lens):
+        """||I - R_gt R_pred^-1||_F per frame (compute.py:338-346), mean over the valid frames; quaternions [M*T,4], mask [M,T]."""
+        M, T = mask.shape
+        Rg = EgoMetrics.quat_to_rotmat(quat_ref.reshape(-1, 4).to(mask.dtype))
+        Rp = EgoMetrics.quat_to_rotmat(quat_pred.reshape(-1, 4).to(mask.dtype))
+        err = (torch.eye(3, device=mask.device, dtype=mask.dtype) - Rg @ torch.linalg.inv(Rp)).flatten(1).norm(dim=1).reshape(M, T)
+        return (err * mask).sum(1) / lens
 
     def update(self, jts_pred, jts_ref, lengths, quat_pred=None, quat_ref=None, split: str = "test",
                jts_int=None, jts_int_gt=None):
@@ -310,6 +317,8 @@ class MLD(nn.Module):
         self.cfg_scene_order = str(cfg.TEST.get("CFG_SCENE_ORDER", "reference"))
         if self.cfg_scene_order not in ("reference", "fixed"):
             raise ValueError("TEST.CFG_SCENE_ORDER must be 'reference' or 'fixed'")
+        # hypotheses per sequence in ONE evaluation pass (condition encoded once, errors and diversity per sequence): 1 = today's path
+        self.num_hypotheses = self._check_num_hypotheses(cfg.TEST.get("NUM_HYPOTHESES", 1), "TEST.NUM_HYPOTHESES")
         self.hip_backward = cfg.TRAIN.get("HIP_BACKWARD", True)   # hand-written backward of the denoiser chain (one head)
         self.hip_vae_backward = cfg.TRAIN.get("HIP_VAE_BACKWARD", True)   # stage 1: hand-written VAE backward (vae_train.py)
         self.hip_glue = cfg.TRAIN.get("HIP_GLUE", True)           # ... and of everything around it (stage2_glue.py); needs HIP_BACKWARD
@@ -361,6 +370,7 @@ class MLD(nn.Module):
         self.optimizer = None          # built lazily: parameters must be on the device first
         self.losses = {k: MLDLosses(cfg) for k in ("train", "val", "test")}
         self.EgoMetric = EgoMetrics()
+        self.HypMetric = HypothesisMetrics()
         self.do_classifier_free_guidance = self.guidance_scale > 1.0
         self.renorm = datamodule.renorm if datamodule is not None else (lambda x: x)
         self.times: List[float] = []
@@ -688,10 +698,17 @@ class MLD(nn.Module):
 
     # ------------------------------------------------------------------ evaluation (mld.py:1076-1905, live part)
     @torch.no_grad()
-    def ego_eval(self, batch, latents=None, want_vertices=False, cond_noise=None, step_noise=None):
+    def ego_eval(self, batch, latents=None, want_vertices=False, cond_noise=None, step_noise=None, num_hypotheses=None):
         """Injection points for parity tests (not in the reference): latents [B,1,256] initial noise; cond_noise = eps
         [1,B,256] of the condition sample (stage 'vae': of the target's sample), or a pair (eps_cond, eps_uncond) with
-        classifier-free guidance; step_noise for DDPM."""
+        classifier-free guidance; step_noise for DDPM.
+
+        num_hypotheses K (None: TEST.NUM_HYPOTHESES) > 1 draws K hypotheses per sequence from ONE encode of the condition
+        (``_ego_eval_hypotheses``): the injection points then have B*K rows, row b*K + k = hypothesis k of sequence b.  K = 1 is the
+        path below, unchanged."""
+        K = self.num_hypotheses if num_hypotheses is None else self._check_num_hypotheses(num_hypotheses, "num_hypotheses")
+        if K > 1:
+            return self._ego_eval_hypotheses(batch, K, latents, want_vertices, cond_noise, step_noise)
         int_gt = None
         if self.pose_estimation_task:       # batch ends with the interactee's ground truth (mld.py:1119-1131)
             batch, int_gt = tuple(batch[:-3]), tuple(t.float() for t in batch[-3:])
@@ -770,6 +787,173 @@ class MLD(nn.Module):
             rs["vertices_ref"], rs["vertices_rst"] = out_ref[1], out_rst[1]
         return rs
 
+    # ------------------------------------------------------------------ K hypotheses per sequence in one pass
+    MAX_SAMPLE_ROWS = 512          # the largest sampling batch that has a cluster plan (one CU per sample above it)
+
+    @staticmethod
+    def _check_num_hypotheses(k, what: str) -> int:
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= K_MAX:
+            raise ValueError(f"{what} must be an integer in 1..{K_MAX}, got {k!r}")
+        return k
+
+    @classmethod
+    def _row_chunks(cls, rows: int):
+        """[lo, hi) ranges of at most MAX_SAMPLE_ROWS rows, evenly sized."""
+        n = -(-rows // cls.MAX_SAMPLE_ROWS)
+        size = -(-rows // n)
+        return [(lo, min(lo + size, rows)) for lo in range(0, rows, size)]
+
+    def _diffusion_reverse_rows(self, cond_bf, rows: int, latents=None, step_noise=None):
+        """_diffusion_reverse on `rows` chains, at most MAX_SAMPLE_ROWS per launch.  cond_bf [rows or 2*rows, N, 256] batch-first
+        (unconditional rows first with guidance).  The draws that are not given are made for all rows at once."""
+        dev = cond_bf.device
+        if latents is None:
+            latents = torch.randn((rows, self.latent_dim[0], self.latent_dim[-1]), device=dev, dtype=torch.float)
+        latents = latents * self.scheduler.init_noise_sigma
+        self.scheduler.set_timesteps(self.cfg.model.scheduler.num_inference_timesteps)
+        eta = 0.0
+        if "eta" in set(inspect.signature(self.scheduler.step).parameters.keys()):
+            eta = self.cfg.model.scheduler.eta
+        if self.scheduler.needs_noise(eta):
+            steps = len(self.scheduler.timesteps)
+            if step_noise is None:
+                step_noise = torch.randn(steps, rows, self.latent_dim[-1], device=dev, dtype=torch.float32)
+            step_noise = step_noise.reshape(steps, rows, self.latent_dim[-1])
+        else:
+            step_noise = None
+        cfg = self.do_classifier_free_guidance
+        out = []
+        for lo, hi in self._row_chunks(rows):
+            c = torch.cat([cond_bf[lo:hi], cond_bf[rows + lo:rows + hi]], dim=0) if cfg else cond_bf[lo:hi]
+            out.append(self.denoiser.sample_loop(latents[lo:hi], c.contiguous(), self.scheduler, eta=eta,
+                                                 guidance_scale=self.guidance_scale if cfg else 1.0,
+                                                 step_noise=None if step_noise is None else step_noise[:, lo:hi]))
+        return out[0] if len(out) == 1 else torch.cat(out, dim=1)            # [1,rows,256]
+
+    def _ego_eval_hypotheses(self, batch, K, latents=None, want_vertices=False, cond_noise=None, step_noise=None):
+        """ego_eval for K > 1.  Once per SEQUENCE: the PointNet scene code and its token (and the zero-scene token under guidance),
+        the image token, vae.encode_dist of the interactee (and of the zero motion), the reference and interactee joints.  Per
+        HYPOTHESIS: the posterior draw of the condition token, the initial latent, the DDPM step noise, decode, renorm, SMPL joints.
+        Rows are sequence-major (b*K + k).  The keys of the K = 1 result are filled from hypothesis 0."""
+        int_gt = None
+        if self.pose_estimation_task:
+            batch, int_gt = tuple(batch[:-3]), tuple(t.float() for t in batch[-3:])
+        eps_c, eps_u = cond_noise if isinstance(cond_noise, (tuple, list)) else (cond_noise, None)
+        feats_ref, transl, beta, utils_, scene, images, length, _ = split_batch(self.condition, batch)
+        B = feats_ref.shape[0]
+        BK = B * K
+        rep = lambda t: t.repeat_interleave(K, dim=1)                       # [1,B,256] -> [1,B*K,256]
+        scene_tok = img_tok = None
+        if images is not None and self.stage != "vae":
+            if self.do_classifier_free_guidance:
+                raise NotImplementedError("ego_eval with an 'image' condition and guidance_scale > 1 (see ego_eval)")
+            img_tok = rep(self._image_token(images))
+            if scene is not None:
+                scene_tok = rep(self._scene_token(scene))
+        elif scene is not None and self.stage != "vae":
+            scene_tok = rep(self._scene_token(scene))
+            if self.do_classifier_free_guidance:                           # halves in the order of ego_eval (TEST.CFG_SCENE_ORDER)
+                unc = rep(self._scene_token(torch.zeros_like(scene)))
+                scene_tok = torch.cat([scene_tok, unc] if self.cfg_scene_order == "reference" else [unc, scene_tok], dim=1)
+        feats_ref, transl, beta = feats_ref.float(), transl.float(), beta.float()
+        lengths = length.long().reshape(-1).tolist()
+        idx_ref = 0 if self.estimate == "wearer" else 1
+
+        def draws(feats, eps):
+            """K posterior draws per sequence from ONE encode: [1,B*K,256]."""
+            dist = self.vae.encode_dist(feats, lengths)
+            mu, std = rep(dist[0:1]), rep(dist[1:2].exp().pow(0.5))
+            if self.sample_mean:
+                return mu
+            if eps is None:
+                eps = torch.empty_like(mu).normal_()
+            return mu + eps.to(mu).reshape(1, BK, -1) * std
+
+        start = time.time()
+        if self.stage in ("diffusion", "vae_diffusion"):
+            text_emb = None
+            if "interactee" in self.condition:
+                f_int = self._wearer_features(feats_ref, transl, 1)
+                text_emb = draws(f_int, eps_c)
+                if self.do_classifier_free_guidance:
+                    text_emb = torch.cat([draws(torch.zeros_like(f_int), eps_u), text_emb], dim=1)
+            toks = [t for t in (text_emb, scene_tok, img_tok) if t is not None]
+            if not toks:
+                raise ValueError("no condition tokens")
+            cond_emb = torch.cat(toks, dim=0)                               # [N, B*K or 2*B*K, 256]
+            z = self._diffusion_reverse_rows(cond_emb.permute(1, 0, 2), BK, latents=latents, step_noise=step_noise)
+        elif self.stage == "vae":                                          # K posterior draws of the target
+            z = draws(self._wearer_features(feats_ref, transl, idx_ref), eps_c)
+        else:
+            raise ValueError(f"Not support this stage {self.stage}!")
+        if self.see_future:
+            lengths = [int(i // 2) for i in lengths]
+        min_len = min(feats_ref.shape[1], int(max(lengths)))
+        f_ref = self.renorm(self._wearer_features(feats_ref[:, :min_len], transl[:, :, :min_len], idx_ref))
+        b_ref = beta[:, idx_ref, :min_len]
+        o_ref = f_ref[:, :, :3] if (self.data_type == "angle" and self.name_dataset == "egobody" and not self.pred_global_orient) else None
+        dev = f_ref.device
+        lengths_k = [l for l in lengths for _ in range(K)]
+        f_rst = torch.zeros(BK, min_len, f_ref.shape[-1], device=dev, dtype=torch.float32)
+        joints_all = torch.empty(BK, min_len, 24, 3, device=dev, dtype=torch.float32)
+        chunks = self._row_chunks(BK)                                       # decode, renorm, SMPL joints of <= 512 rows at a time
+        decoded = [self.vae.decode(z[:, lo:hi], lengths_k[lo:hi]) for lo, hi in chunks]
+        self.times.append(time.time() - start)
+        for (lo, hi), feats_c in zip(chunks, decoded):                      # feats_c [n, max length of the chunk, F], zeros past each length
+            tc = min(min_len, feats_c.shape[1])
+            if tc == min_len:
+                fc = feats_c[:, :min_len].contiguous()
+            else:
+                fc = torch.zeros(hi - lo, min_len, feats_c.shape[-1], device=dev, dtype=torch.float32)
+                fc[:, :tc] = feats_c[:, :tc]
+            fc = self.renorm(fc)
+            seq = torch.arange(lo, hi, device=dev) // K
+            f_rst[lo:hi] = fc
+            joints_all[lo:hi] = self._feats_to_joints(fc, b_ref[seq], orient=None if o_ref is None else o_ref[seq])
+        del decoded
+        out_ref = self._feats_to_joints(f_ref, b_ref, want_vertices)
+        joints_ref = out_ref[0] if want_vertices else out_ref
+        f_rst0 = f_rst.view(B, K, min_len, -1)[:, 0].contiguous()
+        joints_all = joints_all.view(B, K, min_len, 24, 3)
+        f_int_r = self.renorm(self._wearer_features(feats_ref[:, :min_len], transl[:, :, :min_len], 1))
+        joints_int = self._feats_to_joints(f_int_r, beta[:, 1, :min_len])
+        joints_int_gt = None
+        if int_gt is not None:
+            g_motion, g_transl, _g_beta = int_gt
+            f_gt = g_motion[:, :min_len, 0]
+            if self.predict_transl:
+                f_gt = torch.cat([f_gt, g_transl[:, 0, :min_len]], dim=-1)
+            joints_int_gt = self._feats_to_joints(self.renorm(f_gt.contiguous()), beta[:, 1, :min_len])
+        if self.data_type == "angle":
+            quat = lambda f, o=None: G.aa_to_quat((f[:, :, :3] if o is None else o).reshape(-1, 3).contiguous())
+        else:
+            quat = lambda f, o=None: None
+        q_ref = quat(f_ref)
+        q_all = quat(f_rst, None if o_ref is None else o_ref.repeat_interleave(K, dim=0))      # [B*K*T,4]
+        # per-hypothesis errors and the diversity of the K draws: one pass of seeme_hyp_metrics over the joints
+        hm = hyp_metrics_hip(joints_all, joints_ref, lengths)
+        lens = torch.as_tensor(lengths, device=dev).reshape(B)
+        if q_all is not None:
+            mask = (torch.arange(min_len, device=dev)[None, :] < lens[:, None]).to(torch.float32).repeat_interleave(K, dim=0)
+            q_ref_k = q_ref.reshape(B, min_len, 4).repeat_interleave(K, dim=0)
+            hm["HEAD_ORIENTATION_ERROR"] = EgoMetrics.head_orientation_error(q_all, q_ref_k, mask, lens.repeat_interleave(K)).reshape(B, K)
+        else:
+            hm["HEAD_ORIENTATION_ERROR"] = torch.zeros(B, K, device=dev, dtype=torch.float32)
+        hm["have_quat"] = q_all is not None
+        # (the 'test' inclusion rule; allsplit_step, which knows the split, puts the 'val' rule's index there on 'val')
+        hm["best_index"] = best_index(hm["MPJPE"], keep_mask(hm, "test", hm["have_quat"]))
+        rs = {"m_ref": f_ref, "m_rst": f_rst0, "joints_ref": joints_ref, "joints_rst": joints_all[:, 0].contiguous(),
+              "orientation_quat_rst": None if q_all is None else q_all.reshape(B, K, min_len, 4)[:, 0].reshape(-1, 4).contiguous(),
+              "orientation_quat_ref": q_ref,
+              "root_interactee": joints_int[:, :, 0], "joints_interactee": joints_int,
+              "orientation_quat_int": quat(f_int_r), "joints_interactee_gt": joints_int_gt, "lengths": lengths,
+              "list_names": {}, "lat_t": z.view(1, B, K, -1)[:, :, 0].contiguous(),
+              "joints_rst_all": joints_all, "m_rst_all": f_rst.view(B, K, min_len, -1), "lat_t_all": z, "hyp_metrics": hm}
+        if want_vertices:                                                   # meshes of hypothesis 0 only (6890 vertices per frame)
+            rs["vertices_ref"] = out_ref[1]
+            rs["vertices_rst"] = self._feats_to_joints(f_rst0, b_ref, True, orient=o_ref)[1]
+        return rs
+
     def forward(self, batch, **kw):
         return self.ego_eval(batch, **kw)
 
@@ -791,6 +975,11 @@ class MLD(nn.Module):
             self.EgoMetric.update(rs_set["joints_rst"], rs_set["joints_ref"], rs_set["lengths"],
                                   rs_set.get("orientation_quat_rst"), rs_set.get("orientation_quat_ref"), split=split,
                                   jts_int=rs_set.get("joints_interactee"), jts_int_gt=rs_set.get("joints_interactee_gt"))
+            if "hyp_metrics" in rs_set:                                    # TEST.NUM_HYPOTHESES > 1
+                hm = rs_set["hyp_metrics"]
+                if split != "test":
+                    hm["best_index"] = best_index(hm["MPJPE"], keep_mask(hm, split, hm["have_quat"]))
+                self.HypMetric.update(hm, split)
         if split == "test":
             return rs_set["joints_rst"]
         return loss
