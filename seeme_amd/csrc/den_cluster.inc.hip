@@ -260,14 +260,87 @@ __device__ __forceinline__ void cl_store_granule(unsigned long long* g, unsigned
 }
 __device__ __forceinline__ unsigned cl_tags_ok(const u32x4& a, unsigned epoch) { return (unsigned)(a.y == epoch) & (unsigned)(a.w == epoch); }   // (no short-circuit branches)
 
-// The next layer's small operands -> the other half of the staging buffer, through registers: only what THIS CU reads (its slices of the
-// in_proj / skip / linear1 biases, the LayerNorm and bias vectors of the replicated stages, the time token's K | V' and the ffn AdaLN rows, the
-// condition token's K | V', the tabulated ca term): 22-23 pieces of at most 1 KiB = 17.9 KB at C = 8, three per wave: one requested at the top
-// of each of the phases B, D and F and stored to LDS at its end, so that the load's latency passes behind the phase.  (As 36 KB of LDS-DMA -- stage_dma, what k_den_sample
-// does -- the same operands cost this kernel 1.9 k cycles per layer: LDS-DMA moves ~40 GB/s per CU, and here nothing overlaps it.)
+// ---- small operands of a layer (everything that is not a matrix).  What THIS CU reads of them falls in two classes:
+//   launch-constant  its slices of the skip / in_proj / linear1 biases, the ten LayerNorm and bias vectors of the replicated stages, the sa
+//                    K | V' of the sample's condition token: 3 200 floats per layer at C = 8 (3 456 at C = 4, 3 968 at C = 2)
+//   changing         the time token's K | V', the ffn AdaLN scale | shift, the tabulated ca term: five rows of 256 floats, selected by the
+//                    table row (step, or sample with per-sample timesteps) and the layer
+// One condition token (!Q): the constant class of ALL five layers is RESIDENT in LDS (ClRes: 64 KB at C = 8), loaded once in the prologue by
+// LDS-DMA; only the five changing rows travel per layer, into the other half of a 2 x 5 KiB double buffer (ClRow).  They are requested by
+// waves 1 .. 5 as the OLDEST loads of the X1 window -- before the wave's share of the window's units -- and stored behind those units, in
+// front of the barrier that closes the window (where these waves wait out the epilogue wave's sweep and vector algebra anyway): vmcnt
+// retires in order, so the store's wait is vmcnt(wave-loads requested behind the row) -- 24 at C = 8: every unit stays in flight -- and
+// the row has had the whole exchange to land.  Phases B .. F request and stage nothing.  (Stored at the END of phase B instead, the row
+// lives across the join of the epilogue wave's and the other waves' paths: the compiler then copies it at the end of the window, with the
+// same vmcnt(24), and counts the first MFMA of B as vmcnt(2) instead of vmcnt(23) -- tried, ISA read, dropped.)
+//   (Before: all 22 pieces of the next layer were re-fetched in every layer of every step, one piece per wave at the top of each of B, D
+//   and F, stored at the phase's end.  The piece was then the NEWEST load of its wave, so the store drained the whole in-order queue --
+//   `s_waitcnt vmcnt(0)` in front of the ds_write of B and D, and at the last MFMA of F -- i.e. the units the windows had requested for
+//   LATER phases: three times per layer the ring that is meant to run ahead was emptied inside a phase of a few hundred cycles of work.)
+// Residency is per launch and in LDS only: nothing survives the kernel, so no weight, condition or scheduler change can be seen stale.
+// Two condition tokens (Q): ~6 000 constant floats per layer do not fit five-fold; ClStage keeps the per-layer staging through registers
+// (26 + NL1 + 4 N pieces of at most 1 KiB, one per wave at the top of each of B, C, H, D, F into the other half of a full-layout double buffer).
+template <int C> struct ClRes {                        // compact layout of one layer's launch-constant operands (floats)
+    static constexpr int S = ClG<C>::S, NB = ClG<C>::NB;
+    static constexpr int SKIP_B = 0, IN_B = S;         // [S] skip_b slice | [3][S] q, k, v' slices of in_b
+    static constexpr int L1B = 4 * S;                  // [NB] linear1 bias slice
+    static constexpr int V5 = L1B + NB;                // n1w n1b l2b n2w n2b   (256 each)
+    static constexpr int F1B = V5 + 5 * 256;           // [FF_D]
+    static constexpr int V4 = F1B + FF_D;              // f2b fsnw fsnb fo_b    (256 each)
+    static constexpr int CT = V4 + 4 * 256;            // sa K | V' of the sample's condition token
+    static constexpr int LAYER = CT + 512;
+    static constexpr int NL1 = NB > 256 ? NB / 256 : 1;
+    static constexpr int NP = 16 + NL1;                // pieces (<= 1 KiB) per layer
+    static constexpr int ROWS = 5 * 256;               // one half of the double buffer: time K | time V' | ffn scale | ffn shift | ca term
+    static constexpr int FLOATS = SEEME_DEN_NL * LAYER + 2 * ROWS;
+};
+// prologue: every layer's launch-constant operands -> the resident block, layer 0's changing rows -> half 0 of the double buffer; LDS-DMA,
+// the pieces dealt over the eight waves (the caller waits vmcnt(0) and synchronises)
+template <int C>
+__device__ __forceinline__ void cl_load_resident(int wave, int lane, float* __restrict__ res, const float* __restrict__ vpg, const DenLayout* __restrict__ lay,
+                                                 const float* __restrict__ tt_row, const SeemeSampleArgs& A, int b, int c, int ca_R) {
+    typedef ClRes<C> R;
+    const uint32_t base = lds_addr_of(res);
+#pragma unroll 1
+    for (int p = wave; p < SEEME_DEN_NL * R::NP + 5; p += DEN_THREADS / 64) {
+        const float* src; int d, n = 64;
+        if (p >= SEEME_DEN_NL * R::NP) {               // layer 0's changing rows (ca row of a shared timestep table: step 0)
+            const int j = p - SEEME_DEN_NL * R::NP;
+            d = SEEME_DEN_NL * R::LAYER + j * 256;
+            src = j < 2 ? tt_row + j * 256 : (j < 4 ? tt_row + 2560 + 512 + (j - 2) * 256 : A.catab + (size_t)b * ca_R * SEEME_DEN_NL * 256);
+        } else {
+            const int l = p / R::NP, i = p - l * R::NP;
+            const DenLayerOff* __restrict__ L = &lay->L[l];
+            const float* vb = vpg + L->skip_b;
+            if (i == 0) { src = vb + c * R::S; d = R::SKIP_B; n = R::S / 4; }
+            else if (i <= 3) { src = vb + (L->in_b - L->skip_b) + (i - 1) * 256 + c * R::S; d = R::IN_B + (i - 1) * R::S; n = R::S / 4; }
+            else if (i <= 8) { const int64_t f = i == 4 ? L->n1w : i == 5 ? L->n1b : i == 6 ? L->l2b : i == 7 ? L->n2w : L->n2b; src = vpg + f; d = R::V5 + (i - 4) * 256; }
+            else if (i == 9) { src = vpg + L->f1b; d = R::F1B; n = FF_D / 4; }
+            else if (i <= 13) { const int64_t f = i == 10 ? L->f2b : i == 11 ? L->fsnw : i == 12 ? L->fsnb : L->fo_b; src = vpg + f; d = R::V4 + (i - 10) * 256; }
+            else if (i <= 15) { src = A.ctab + (size_t)b * SEEME_CROW + l * 512 + (i - 14) * 256; d = R::CT + (i - 14) * 256; }
+            else { src = vpg + L->l1b + c * R::NB + (i - 16) * 256; d = R::L1B + (i - 16) * 256; n = R::NB >= 256 ? 64 : R::NB / 4; }
+            d += l * R::LAYER;
+        }
+        if (lane < n) lds_dma_1k(src + 4 * lane, base + (uint32_t)d * 4u);
+    }
+}
+// one changing row of the NEXT layer per wave (waves 1 .. 5 hold rows 0 .. 4; waves 6, 7 request a row again and drop it, so that no branch
+// stands around the load): all 64 lanes load, 4 registers live inside the X1 window only
+struct ClRow {
+    float4 r;
+    __device__ __forceinline__ void load(int wave, int lane, const float* __restrict__ tt_row, const float* __restrict__ ca_row, int l) {
+        const int j = wave - 1 - (wave > 5 ? 5 : 0);
+        const float* src = j < 2 ? tt_row + l * 512 + j * 256 : (j < 4 ? tt_row + 2560 + l * 1024 + 512 + (j - 2) * 256 : ca_row);
+        r = *reinterpret_cast<const float4*>(src + 4 * lane);
+    }
+    __device__ __forceinline__ void store(int wave, int lane, float* __restrict__ rows) const {
+        if (wave >= 1 && wave <= 5) *reinterpret_cast<float4*>(rows + (wave - 1) * 256 + 4 * lane) = r;
+    }
+};
+
 template <int C, bool Q>
 struct ClStage {
-    float4 r; int dst, n4;        // ONE piece per wave and phase (!Q: k = 0 in phase B, 1 in D, 2 in F; Q: B, C, H, D, F): 4 registers live across a phase
+    float4 r; int dst, n4;        // ONE piece per wave and phase (Q: k = 0 .. 4 in phases B, C, H, D, F): 4 registers live across a phase
     static constexpr int NL1 = ClG<C, Q>::NB > 256 ? ClG<C, Q>::NB / 256 : 1;
     __device__ __forceinline__ void load(int k, int wave, int lane, const float* __restrict__ vpg, const DenLayerOff* __restrict__ L,
                                          const float* __restrict__ tt_row, int l, const SeemeSampleArgs& A, int b, int c, int ca_r, int ca_R) {
@@ -286,11 +359,7 @@ struct ClStage {
         else if (i <= 15) { src = tt_row + l * 512 + (i - 14) * 256; d = VP_LAYER + (i - 14) * 256; n = 64; }                 // time token K | V'
         else if (i <= 17) { src = tt_row + 2560 + l * 1024 + 512 + (i - 16) * 256; d = VP_LAYER + 1024 + (i - 16) * 256; n = 64; }   // ffn AdaLN scale | shift
         else if (i < 18 + NL1) { d = (int)(L->l1b - L->skip_b) + c * G::NB + (i - 18) * 256; src = vb + d; n = G::NB >= 256 ? 64 : G::NB / 4; }
-        else if constexpr (!Q) {
-            const int j = i - 18 - NL1;
-            if (j <= 1) { src = A.ctab + (size_t)b * SEEME_CROW + l * 512 + j * 256; d = VP_LAYER + STG_TT + j * 256; n = 64; }             // sa K | V' of the condition token
-            else if (j == 2) { src = A.catab + (((size_t)b * ca_R + ca_r) * SEEME_DEN_NL + l) * 256; d = VP_LAYER + STG_TT + 1024; n = 64; }   // its tabulated ca term
-        } else {
+        else {
             const int j = i - 18 - NL1;
             if (j <= 1) { src = tt_row + 2560 + l * 1024 + j * 256; d = VP_LAYER + 512 + j * 256; n = 64; }                                 // ca AdaLN scale | shift
             else if (j <= 6) {
@@ -312,7 +381,7 @@ struct ClStage {
         if (lane < n4) *reinterpret_cast<float4*>(stg + dst + 4 * lane) = r;
     }
 };
-// pieces: !Q 21 + NL1 <= 24 (three phases x 8 waves); Q 26 + NL1 + 4 N <= 40 (five phases) for N <= 2 (C = 2: N = 2 gives 36)
+// pieces (Q): 26 + NL1 + 4 N <= 40 (five phases x 8 waves) for N <= 2 (C = 2: N = 2 gives 36)
 #define DCL_MAX_N 2
 
 template <typename WT, int C, bool Q>
@@ -337,13 +406,16 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
     if (b >= A.B) return;                                      // (whole clusters: every member sees the same b)
     const bool epi = wave == 0;
     const int N = Q ? A.N : 1;
-    const int stg_sz = VP_LAYER + STG_TT + N * 1024 + (Q ? 0 : 256);
+    typedef ClRes<C> R;
+    constexpr bool RSD = !Q;                     // launch-constant operands resident in LDS (ClRes); Q: per-layer staging (ClStage)
+    const int stg_sz = VP_LAYER + STG_TT + N * 1024;             // (Q) one half of the staging buffer, full layout
     const int ca_R = A.trow_per_sample ? 1 : A.steps;
 
     float* CONSTV = smem;                        // [768]  query_pos.pe[0], encoder.norm.{weight,bias}
     float* KEEP = CONSTV + 768;                  // [256]  the latent (epilogue wave)
-    float* STG = KEEP + 256;                     // [2][stg_sz] per-layer operands, double-buffered (stage_dma)
-    float* XA = STG + 2 * stg_sz;                // [512]  GEMV input: layer input x / x2   (16-bit: fragments of 256 k = 2 KiB)
+    float* STG = KEEP + 256;                     // RSD: [5][R::LAYER] resident operands | [2][R::ROWS] changing rows;  Q: [2][stg_sz] per-layer operands
+    float* ROWS = STG + SEEME_DEN_NL * R::LAYER; // (RSD)
+    float* XA = STG + (RSD ? R::FLOATS : 2 * stg_sz);   // [512]  GEMV input: layer input x / x2   (16-bit: fragments of 256 k = 2 KiB)
     float* XB = XA + 512;                        // [512]  GEMV input: x1 / u
     float* XH = XB + 512;                        // [2 NB] GEMV input: this CU's hidden units / ffn hidden (fragments of NB k)
     float* SKF = XH + 2 * (G::NB > 128 ? G::NB : 128);   // [2][512] outputs of layers 0, 1 (skip inputs of layers 4, 3)
@@ -369,11 +441,12 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
     const CF32 coef_c = (CF32)(uintptr_t)A.coef;
     int row = A.trow_per_sample ? trow_c[b] : trow_c[0];
 
-    // ---- prologue: constants, layer 0 operands, zeroed fragment buffers, first input, first RU units, the XCC census
+    // ---- prologue: constants, small operands (resident: all layers; Q: layer 0), zeroed fragment buffers, first input, first RU units, the XCC census
     float4 xr = ld4(A.latents + (size_t)b * 256 + 4 * lane);
     for (int i = tid; i < 192; i += DEN_THREADS)
         st4(CONSTV + 4 * i, i < 64 ? ld4(vp + lay->pe0 + 4 * i) : (i < 128 ? ld4(vp + lay->fnw + 4 * (i - 64)) : ld4(vp + lay->fnb + 4 * (i - 128))));
-    stage_dma<1, Q, 0, 0>(wave, lane, STG, vp, &lay->L[0], A.ttab + (size_t)row * SEEME_TROW, 0, A, b, N, 0, ca_R);
+    if constexpr (RSD) cl_load_resident<C>(wave, lane, STG, vp, lay, A.ttab + (size_t)row * SEEME_TROW, A, b, c, ca_R);
+    else stage_dma<1, Q, 0, 0>(wave, lane, STG, vp, &lay->L[0], A.ttab + (size_t)row * SEEME_TROW, 0, A, b, N, 0, ca_R);
     for (int i = tid; i < XZERO / 4; i += DEN_THREADS) st4(XA + 4 * i, make_float4(0.f, 0.f, 0.f, 0.f));
     if (tid >= 1 && tid < 4) FLG[tid] = 0;                   // window flags (epochs are never 0)
     bool dead = false, local = false;
@@ -424,22 +497,33 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
             const DenLayerOff* __restrict__ Ln = &lay->L[ln];
             const bool skip = l >= 3, nskip = ln >= 3;
             const unsigned bc = (unsigned)((l * C + c) * G::NU) * W::UNIT_BYTES, bn = (unsigned)((ln * C + c) * G::NU) * W::UNIT_BYTES;
-            const float* VP = STG + cur * stg_sz;
-            const float* TTS = VP + VP_LAYER;
-            const float* CT = TTS + STG_TT;
-            const float* CA_ADD = CT + N * 1024;
-            const float* v_skip_b = VP;
-            const float* v_in_b = VP + (L->in_b - L->skip_b);
-            const float* v_n1w = VP + (L->n1w - L->skip_b), *v_n1b = VP + (L->n1b - L->skip_b);
-            const float* v_l1b = VP + (L->l1b - L->skip_b), *v_l2b = VP + (L->l2b - L->skip_b);
-            const float* v_n2w = VP + (L->n2w - L->skip_b), *v_n2b = VP + (L->n2b - L->skip_b);
-            const float* v_f1b = VP + (L->f1b - L->skip_b), *v_f2b = VP + (L->f2b - L->skip_b);
-            const float* v_fsnw = VP + (L->fsnw - L->skip_b), *v_fsnb = VP + (L->fsnb - L->skip_b);
-            const float* v_fo_b = VP + (L->fo_b - L->skip_b);
+            // small operands: layer l of the resident block + the current half of the changing rows (RSD), or the current half of the
+            // staging buffer in the layout of the vector-parameter image (Q).  v_skip_b, v_in_b and v_l1b hold this CU's slices only
+            // when resident: IN_ST = distance of the q, k, v' parts of in_b, d0 / j0 = this CU's first dim / hidden unit in them.
+            const float* VP = STG + (RSD ? l * R::LAYER : cur * stg_sz);
+            const float* TTS = RSD ? ROWS + cur * R::ROWS : VP + VP_LAYER;        // time token K | V' ...
+            const float* TFS = TTS + (RSD ? 512 : 1024);                          // ... ffn AdaLN scale | shift
+            const float* CT = RSD ? VP + R::CT : TTS + STG_TT;
+            const float* CA_ADD = TTS + 1024;                                     // (RSD) the tabulated ca term
+            constexpr int IN_ST = RSD ? G::S : 256;
+            const int d0 = RSD ? 0 : c * G::S, j0 = RSD ? 0 : c * G::NB;
+            const float* v_skip_b = RSD ? VP + R::SKIP_B : VP;
+            const float* v_in_b = RSD ? VP + R::IN_B : VP + (L->in_b - L->skip_b);
+            const float* v_n1w = RSD ? VP + R::V5 : VP + (L->n1w - L->skip_b), *v_n1b = RSD ? VP + R::V5 + 256 : VP + (L->n1b - L->skip_b);
+            const float* v_l1b = RSD ? VP + R::L1B : VP + (L->l1b - L->skip_b), *v_l2b = RSD ? VP + R::V5 + 512 : VP + (L->l2b - L->skip_b);
+            const float* v_n2w = RSD ? VP + R::V5 + 768 : VP + (L->n2w - L->skip_b), *v_n2b = RSD ? VP + R::V5 + 1024 : VP + (L->n2b - L->skip_b);
+            const float* v_f1b = RSD ? VP + R::F1B : VP + (L->f1b - L->skip_b), *v_f2b = RSD ? VP + R::V4 : VP + (L->f2b - L->skip_b);
+            const float* v_fsnw = RSD ? VP + R::V4 + 256 : VP + (L->fsnw - L->skip_b), *v_fsnb = RSD ? VP + R::V4 + 512 : VP + (L->fsnb - L->skip_b);
+            const float* v_fo_b = RSD ? VP + R::V4 + 768 : VP + (L->fo_b - L->skip_b);
             const float* v_cnw = VP + (L->cnw - L->skip_b), *v_cnb = VP + (L->cnb - L->skip_b), *v_caq_b = VP + (L->caq_b - L->skip_b);
             const float* v_csnw = VP + (L->csnw - L->skip_b), *v_csnb = VP + (L->csnb - L->skip_b), *v_cao_b = VP + (L->cao_b - L->skip_b);
-            (void)v_cnw; (void)v_cnb; (void)v_caq_b; (void)v_csnw; (void)v_csnb; (void)v_cao_b;
+            (void)CA_ADD; (void)v_cnw; (void)v_cnb; (void)v_caq_b; (void)v_csnw; (void)v_csnb; (void)v_cao_b;
             const bool ywave = wave >= 6;
+            // the next layer's changing operands: table row of the next step behind the last layer
+            const float* const tt_next = A.ttab + (size_t)(ln == 0 ? row_next : row) * SEEME_TROW;
+            const int ca_next = A.trow_per_sample ? 0 : (ln == 0 ? step_next : step);
+            ClStage<C, true> nxt;       // (Q)
+            (void)nxt; (void)ca_next;
             const unsigned e1 = 1u + (unsigned)G::EPL * (unsigned)(step * SEEME_DEN_NL + l), e2 = e1 + 1u, e3 = e1 + 2u;   // epochs of this layer's exchanges
             (void)e3;
 
@@ -456,12 +540,12 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
                 if (act && lane < 16) {
 #pragma unroll
                     for (int t = 0; t < G::TA; ++t) {
-                        const int T = wave * G::TA + t, part = T / (G::S / 16), d = (T % (G::S / 16)) * 16 + col, D = c * G::S + d;
+                        const int T = wave * G::TA + t, part = T / (G::S / 16), d = (T % (G::S / 16)) * 16 + col, D = d0 + d;
                         const float val = cl_out<WT>(acc[t]);
                         const unsigned epoch = e1;
                         if (part == 0) QS[d] = val + v_in_b[D];
-                        else if (part == 1) KS[d] = val + v_in_b[256 + D];
-                        else if (part == 2) cl_store_granule(xg + G::G_X1 + c * G::X1_G + d, epoch, val + v_in_b[512 + D], local);
+                        else if (part == 1) KS[d] = val + v_in_b[IN_ST + D];
+                        else if (part == 2) cl_store_granule(xg + G::G_X1 + c * G::X1_G + d, epoch, val + v_in_b[2 * IN_ST + D], local);
                         else cl_store_granule(xg + G::G_X1 + c * G::X1_G + G::S + d, epoch, val + v_skip_b[D], local);
                     }
                 }
@@ -550,21 +634,29 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
                 if (skip) xr = make_float4(__uint_as_float(gy0.x), __uint_as_float(gy0.z), __uint_as_float(gy1.x), __uint_as_float(gy1.z));
                 xr = wave_ln(f4_add(xr, att), v_n1w, v_n1b, lane);        // the "values" carry out_proj: residual + norm1
                 put_x<WT, 1>(XB, 0, 0, lane, xr);
-            } else if constexpr (WIN) {
-                cl_flag_wait(FLG + 1, e1);
-                cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W1A{});
-                cl_flag_wait(FLG + 2, e1);
-                cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W1B{});
+            } else {
+                // the next layer's changing row first: the OLDEST load of the window.  It is stored behind the window's units, in front of the
+                // barrier at which these waves wait out the epilogue wave's sweep and vector algebra anyway: the store's wait is
+                // vmcnt(units requested behind the row) -- it leaves every unit in flight and the row has had the whole exchange to land.
+                ClRow nrow;
+                if constexpr (WIN) cl_flag_wait(FLG + 1, e1);
+                if constexpr (RSD) {
+                    nrow.load(wave, lane, tt_next, A.catab + (((size_t)b * ca_R + ca_next) * SEEME_DEN_NL + ln) * 256, ln);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if constexpr (WIN) {
+                    cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W1A{});
+                    cl_flag_wait(FLG + 2, e1);
+                    cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W1B{});
+                }
+                if constexpr (RSD) nrow.store(wave, lane, ROWS + (cur ^ 1) * R::ROWS);
             }
             __syncthreads(); DEN_DBG(0);
 
             // ================= B: linear1 + ReLU, column-split =================
-            // (a piece of the next layer's small operands is requested here and stored to the other half of the staging buffer at the end
+            // (Q: a piece of the next layer's small operands is requested here and stored to the other half of the staging buffer at the end
             //  of the phase -- BEFORE the deferred re-fills: vmcnt is in order, and the store must not wait for them)
-            ClStage<C, Q> nxt;
-            const float* const tt_next = A.ttab + (size_t)(ln == 0 ? row_next : row) * SEEME_TROW;
-            const int ca_next = A.trow_per_sample ? 0 : (ln == 0 ? step_next : step);
-            nxt.load(0, wave, lane, vp, Ln, tt_next, ln, A, b, c, ca_next, ca_R);
+            if constexpr (Q) nxt.load(0, wave, lane, vp, Ln, tt_next, ln, A, b, c, ca_next, ca_R);
             if constexpr (!WIN) cl_refills<WT, C, Q, G::U_A + A_DEF0>(ring, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, 2 * G::TA - A_DEF0>{});   // slots of stage A
             {
                 f32x4 acc[G::TB];
@@ -574,11 +666,11 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
 #pragma unroll
                     for (int t = 0; t < G::TB; ++t) {
                         const int j = (wave * G::TB + t) * 16 + col;
-                        cl_put1<WT>(XH, j, fmaxf(cl_out<WT>(acc[t]) + v_l1b[c * G::NB + j], 0.f));
+                        cl_put1<WT>(XH, j, fmaxf(cl_out<WT>(acc[t]) + v_l1b[j0 + j], 0.f));
                     }
                 }
             }
-            nxt.store(lane, STG + (cur ^ 1) * stg_sz);
+            if constexpr (Q) nxt.store(lane, STG + (cur ^ 1) * stg_sz);
             __syncthreads(); DEN_DBG(0);
 
             // ================= C: linear2, row-split -> X2 =================
@@ -768,7 +860,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
             }
 
             // ================= D: ffn.linear1 + GELU (replicated) =================
-            nxt.load(Q ? 3 : 1, wave, lane, vp, Ln, tt_next, ln, A, b, c, ca_next, ca_R);
+            if constexpr (Q) nxt.load(3, wave, lane, vp, Ln, tt_next, ln, A, b, c, ca_next, ca_R);
             if constexpr (!Q && !WIN) cl_refills<WT, C, Q, G::U_C + C_INL>(ring, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, G::TB - C_INL>{});       // slots of stage C
             {
                 f32x4 acc[1];
@@ -779,7 +871,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
                     cl_put1<WT>(XH, j, fast_gelu(cl_out<WT>(acc[0]) + v_f1b[j]));
                 }
             }
-            nxt.store(lane, STG + (cur ^ 1) * stg_sz);
+            if constexpr (Q) nxt.store(lane, STG + (cur ^ 1) * stg_sz);
             __syncthreads(); DEN_DBG(0);
             // ================= E: ffn.linear2 -> LayerNorm, AdaLN, SiLU (replicated) =================
             {
@@ -795,7 +887,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
                     if (lane == 0) cl_flag_set(FLG + 3, e2);
                 }
                 const float4 y2 = f4_add(ld4(PART + 4 * lane), ld4(v_f2b + 4 * lane));
-                const float4 hh = f4_adaln(wave_ln(y2, v_fsnw, v_fsnb, lane), ld4(TTS + 1024 + 4 * lane), ld4(TTS + 1280 + 4 * lane));
+                const float4 hh = f4_adaln(wave_ln(y2, v_fsnw, v_fsnb, lane), ld4(TFS + 4 * lane), ld4(TFS + 256 + 4 * lane));
                 put_x<WT, 1>(XB, 0, 0, lane, f4_silu(hh));
             } else if constexpr (WIN) {
                 cl_flag_wait(FLG + 3, e2);
@@ -803,7 +895,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
             }
             __syncthreads(); DEN_DBG(0);
             // ================= F: ffn.proj_out.out_layers + residual (replicated); writes the next layer's input =================
-            nxt.load(Q ? 4 : 2, wave, lane, vp, Ln, tt_next, ln, A, b, c, ca_next, ca_R);
+            if constexpr (Q) nxt.load(4, wave, lane, vp, Ln, tt_next, ln, A, b, c, ca_next, ca_R);
             if constexpr (WIN) cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::PF{});
             {
                 f32x4 acc[2];
@@ -818,7 +910,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
                     if (l < 2) cl_put1<WT>(SKF + 512 * l, n, xn);                      // xs.append(x) (cross_attention.py:70-72)
                 }
             }
-            nxt.store(lane, STG + (cur ^ 1) * stg_sz);
+            if constexpr (Q) nxt.store(lane, STG + (cur ^ 1) * stg_sz);
             // (phantom units that pad the layer program are never consumed: the re-fills they would trigger go out here)
             if constexpr (!WIN) cl_refills<WT, C, Q, G::NU_REAL>(ring, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, G::NU - G::NU_REAL>{});
             __syncthreads(); DEN_DBG(0);
@@ -868,8 +960,8 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
 template <int C>
 static size_t cl_lds_bytes(int N, bool q) {
     typedef ClG<C> G;
-    const int stg_sz = VP_LAYER + STG_TT + N * 1024 + (q ? 0 : 256);
-    return (size_t)(768 + 256 + 2 * stg_sz + 512 + 512 + 2 * (G::NB > 128 ? G::NB : 128) + 1024 + 2 * G::S + 256 + 256 + 4) * sizeof(float);
+    const int stg = q ? 2 * (VP_LAYER + STG_TT + N * 1024) : ClRes<C>::FLOATS;    // (one condition token: resident block + changing rows)
+    return (size_t)(768 + 256 + stg + 512 + 512 + 2 * (G::NB > 128 ? G::NB : 128) + 1024 + 2 * G::S + 256 + 256 + 4) * sizeof(float);
 }
 
 extern "C" size_t seeme_den_cluster_xchg_bytes(int B, int C) {       // (the several-token layout: the larger of the two)
