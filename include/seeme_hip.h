@@ -526,6 +526,44 @@ size_t seeme_hyp_metrics_workspace_bytes(int B, int K, int T);
 int seeme_hyp_metrics(const float* jts_pred, const float* jts_ref, const int32_t* lengths, int B, int K, int T,
                       float* per_hyp, float* per_seq, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ ResNet-50 image backbone (csrc/resnet.hip)
+ * EgoHMR.models.resnet.ResNet(Bottleneck, [3,4,6,3]) without fc, frozen and in eval mode: proscene.encode_image
+ * (prohmr_scene.py:99-100).  Every BatchNorm is folded on the host (float64) into its convolution:
+ * w' = w * g / sqrt(var + 1e-5), bias = b - mean * g / sqrt(var + 1e-5).  Activations are NHWC; a convolution is an implicit GEMM
+ * (M = B Ho Wo, N = cout, K = k k cin), epilogue + bias, + residual, ReLU, store.
+ * Packed weight of one convolution, element size s (4: fp32, 2: bf16), E = 16 / s elements per 16-byte chunk:
+ *   Wk[cout][K]: K = (kh, kw, cin) with cin fastest; the stem's cin 3 is zero padded to E (one chunk per tap) and its K to 56 chunks;
+ *   Wp[cout/16][K/(4E)][lane 64][E], lane = 16 kq + r:  Wp[t][g][16 kq + r][e] = Wk[row(t, r)][(4 g + kq) E + e],
+ *   row(t, r) = 64 (t/4) + 16 (r/4) + 4 (t%4) + r%4   (a lane of the kernel then owns 16 consecutive output channels). */
+enum { SEEME_RESNET_FP32 = 0, SEEME_RESNET_BF16 = 1 };
+enum { SEEME_IMG_F32_NCHW = 0,      /* float32 [B,3,224,224], already normalised (the reference's batch slot) */
+       SEEME_IMG_U8_NHWC = 1 };     /* uint8 [B,224,224,3] RGB; normalised in the stem's loader: (x - 255 mean_c) / (255 std_c) */
+#define SEEME_RESNET50_NCONV 53
+typedef struct {
+    const float* weight;            /* packed fp32 fragments (NULL in a bf16 table) */
+    const uint16_t* weight_bf16;    /* packed bf16 fragments (NULL in an fp32 table) */
+    const float* bias;              /* [cout] fp32, the folded BatchNorm shift */
+    int cin, cout, k, stride;       /* padding is k/2 */
+} SeemeConv;
+typedef struct {
+    int precision;                  /* SEEME_RESNET_FP32: every tensor fp32, v_mfma_f32_16x16x4_f32 (parity path);
+                                     * SEEME_RESNET_BF16: bf16 weights and activations, fp32 accumulation and epilogue */
+    SeemeConv conv[SEEME_RESNET50_NCONV];   /* conv1; then per bottleneck conv1, conv2, conv3 and, in a layer's first one, downsample.0 */
+    void* tap[5];                   /* bring-up, normally NULL: device copies of the NHWC activations after the max-pool and after
+                                     * layer1..4 ([B,56,56,64], [B,56,56,256], [B,28,28,512], [B,14,14,1024], [B,7,7,2048]) */
+} SeemeResnet50;
+size_t seeme_resnet50_workspace_bytes(int B, int precision);      /* 0 for a bad B (1..1024) or precision */
+/* images (image_format above) -> out [B,2048] fp32 = mean over the 7x7 map of layer4.  No allocation, no synchronisation, no
+ * atomics; everything is enqueued on `stream` (capturable); workspace 256-byte aligned. */
+int seeme_resnet50_encode(const SeemeResnet50* w, const void* images, int image_format, int B, float* out, void* ws,
+                          size_t ws_bytes, void* stream);
+/* The pieces of the network one by one (tests, bring-up); x / residual / y NHWC in the precision's element type, 16-byte aligned.
+ * seeme_resnet_conv: cin 3 (the stem: x is the output of seeme_resnet_stem_pack) or a power of two >= 16 bytes, cout % 64 == 0. */
+int seeme_resnet_conv(const SeemeConv* c, int precision, const void* x, int B, int H, int W, const void* residual, int relu,
+                      void* y, void* stream);
+int seeme_resnet_stem_pack(const void* images, int image_format, int B, int H, int W, int precision, void* y, void* stream);
+int seeme_resnet_maxpool(int precision, const void* x, int B, int H, int W, int C, void* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,20 @@ class GlueMid(C.Structure):
                 ("g_tn_w", fp * 5), ("g_tn_b", fp * 5), ("dcond", fp), ("dea", fp), ("deb", fp), ("emb", fp), ("demb", fp)]
 
 
+RESNET_FP32, RESNET_BF16 = 0, 1
+IMG_F32_NCHW, IMG_U8_NHWC = 0, 1
+RESNET50_NCONV = 53
+
+
+class Conv(C.Structure):
+    _fields_ = [("weight", fp), ("weight_bf16", fp), ("bias", fp), ("cin", C.c_int), ("cout", C.c_int), ("k", C.c_int),
+                ("stride", C.c_int)]
+
+
+class Resnet50(C.Structure):
+    _fields_ = [("precision", C.c_int), ("conv", Conv * RESNET50_NCONV), ("tap", fp * 5)]
+
+
 GEO_AA_TO_QUAT, GEO_AA_TO_ROTMAT, GEO_QUAT_TO_ROTMAT, GEO_ROT6D_PROHMR, GEO_ROT6D_DIFFUSION = range(5)
 
 # name -> (restype, argtypes); every symbol of include/seeme_hip.h
@@ -194,6 +208,11 @@ _SIGNATURES = {
     "seeme_smpl_lbs": (C.c_int, [C.POINTER(SmplModel), fp, fp, C.c_int, fp, C.c_int, fp, fp, fp, C.c_size_t, fp]),
     "seeme_hyp_metrics_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "seeme_hyp_metrics": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, C.c_int, fp, fp, fp, C.c_size_t, fp]),
+    "seeme_resnet50_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "seeme_resnet50_encode": (C.c_int, [C.POINTER(Resnet50), fp, C.c_int, C.c_int, fp, fp, C.c_size_t, fp]),
+    "seeme_resnet_conv": (C.c_int, [C.POINTER(Conv), C.c_int, fp, C.c_int, C.c_int, C.c_int, fp, C.c_int, fp, fp]),
+    "seeme_resnet_stem_pack": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp]),
+    "seeme_resnet_maxpool": (C.c_int, [C.c_int, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp]),
 }
 
 _lib: Optional[C.CDLL] = None

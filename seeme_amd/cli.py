@@ -139,7 +139,7 @@ def build(cfg, dev, args, datamodule=None, smpl_model=None):
                                    predict_transl=bool(cfg.TRAIN.ABLATION.PREDICT_TRANSL), device=dev, storage=args.storage,
                                    scene_root=args.scene_root, pose_estimation_task=bool(cfg.TEST.get("POSE_ESTIMATION_TASK", False)),
                                    interactee_pred=bool(cfg.TEST.get("INTERACTEE_PRED", False)),      # get_data.py:196
-                                   seed=int(cfg.SEED_VALUE))
+                                   seed=int(cfg.SEED_VALUE), image_backbone=bool(cfg.model.get("image_backbone", False)))
     dm = datamodule or SyntheticEgoDataModule(nfeats=nfeats, T=args.frames, n_points=args.scene_points,
                                                seed=int(cfg.SEED_VALUE), device=dev)
     if smpl_model is None and not os.path.exists(str(cfg.model.smpl_path)):
@@ -152,8 +152,11 @@ def _with_scene(cfg) -> bool:
     return "scene" in cfg.model.condition
 
 
-def _with_image(cfg) -> bool:
-    return "image" in cfg.model.condition
+def _with_image(cfg):
+    """False, True (pooled features) or "crops" (model.image_backbone: uint8 crops for the HIP ResNet-50)."""
+    if "image" not in cfg.model.condition:
+        return False
+    return "crops" if bool(cfg.model.get("image_backbone", False)) else True
 
 
 # ----------------------------------------------------------------------------- train

@@ -33,6 +33,10 @@ On-disk layout (what the reference reads; the datasets themselves are licence-ga
         ``proscene.encode_image`` returns; the backbone runs outside this package).  As in the reference
         (dataset.py:1657-1706) every access draws one frame of the sequence uniformly at random, in every split: on the device from
         a seedable generator (or from injected draws).
+    With ``image_backbone`` (model.image_backbone: the ResNet-50 runs in this package) the frames come as crops instead:
+        <root>/image_crops_<split>.npy uint8 [F,224,224,3] RGB (the patch of dataset.py:1664-1690 before normalisation; opened
+        memory-mapped, only the split's frames are read) and <root>/image_crop_names_<split>.npy, a unicode array [F] of the names.
+        The image slot of a batch is then uint8 NHWC [B,224,224,3]; the frame draw is the same.
 
 Files are read with loaders that execute nothing: ``np.load(allow_pickle=False)`` for arrays, and for the pickled ``.npy`` /
 ``.pkl`` containers an unpickler that only admits numpy array reconstruction and plain containers.
@@ -90,7 +94,7 @@ class EgoSequenceSplit:
     def __init__(self, root: str, split: str, dataset: str = "egobody", condition: Sequence[str] = ("text", "interactee"),
                  motion_length: int = 60, data_type: str = "angle", predict_transl: bool = True,
                  pose_estimation_task: bool = False, scene_root: Optional[str] = None, max_items: Optional[int] = None,
-                 interactee_pred: Optional[str] = None, scene_points: int = 20000):
+                 interactee_pred: Optional[str] = None, scene_points: int = 20000, image_backbone: bool = False):
         if data_type != "angle":
             raise NotImplementedError("data module: DATA_TYPE 'angle' (the rot6d variant re-encodes the same files)")
         self.dataset, self.split, self.condition = dataset, split, tuple(condition)
@@ -172,7 +176,10 @@ class EgoSequenceSplit:
             if pe:
                 raise NotImplementedError("POSE_ESTIMATION_TASK with an 'image' condition: the reference's image layouts carry no interactee "
                                           "ground truth (dataset.py:1788-1792)")
-            self._load_image_feats(os.path.join(root, f"image_feats_{split}.npz"))
+            if image_backbone:
+                self._load_image_crops(os.path.join(root, f"image_crops_{split}.npy"), os.path.join(root, f"image_crop_names_{split}.npy"))
+            else:
+                self._load_image_feats(os.path.join(root, f"image_feats_{split}.npz"))
 
     def _load_image_feats(self, path: str):
         """The feature table of the split and, per sequence, the table rows of its frames (flat, with offsets and counts)."""
@@ -191,6 +198,32 @@ class EgoSequenceSplit:
             raise ValueError(f"split '{self.split}': a sequence without frames cannot draw an image")
         self.image_table = torch.from_numpy(np.ascontiguousarray(feats))                              # [F,2048], the file's dtype
         self.image_rows = torch.from_numpy(np.array([row[im] for ims in self.images for im in ims], np.int64))
+        self.image_cnt = torch.from_numpy(cnt)
+        self.image_off = torch.from_numpy(np.concatenate([[0], np.cumsum(cnt)[:-1]]).astype(np.int64))
+
+    def _load_image_crops(self, path: str, names_path: str):
+        """The crop table of the split (uint8 [F,224,224,3], only the rows its sequences use) and the per-sequence row lists."""
+        for p in (path, names_path):
+            if not os.path.exists(p):
+                raise FileNotFoundError(f"'image' condition with the backbone: {p} is missing (crops uint8 [F,224,224,3] RGB + a unicode "
+                                        "array of their names); see INTEGRATION.md")
+        names = np.load(names_path, allow_pickle=False)
+        if names.dtype.kind != "U" or names.ndim != 1:
+            raise ValueError(f"{names_path}: expected a 1-D unicode array of frame names, got {names.dtype} {names.shape}")
+        crops = np.load(path, mmap_mode="r", allow_pickle=False)
+        if crops.dtype != np.uint8 or crops.ndim != 4 or tuple(crops.shape[1:]) != (224, 224, 3) or crops.shape[0] != len(names):
+            raise ValueError(f"{path}: crops are {crops.shape} {crops.dtype}, names {len(names)}: expected uint8 [F,224,224,3], one per name")
+        row = {str(n): i for i, n in enumerate(names)}
+        missing = [im for ims in self.images for im in ims if im not in row]
+        if missing:
+            raise KeyError(f"{path} lacks the crops of {len(missing)} frame(s) of split '{self.split}', e.g. {missing[:5]}")
+        cnt = np.array([len(ims) for ims in self.images], np.int64)
+        if (cnt == 0).any():
+            raise ValueError(f"split '{self.split}': a sequence without frames cannot draw an image")
+        used = sorted({row[im] for ims in self.images for im in ims})          # file rows of this split's frames, read once
+        local = {r: i for i, r in enumerate(used)}
+        self.image_table = torch.from_numpy(np.ascontiguousarray(crops[used]))                        # [F',224,224,3] uint8
+        self.image_rows = torch.from_numpy(np.array([local[row[im]] for ims in self.images for im in ims], np.int64))
         self.image_cnt = torch.from_numpy(cnt)
         self.image_off = torch.from_numpy(np.concatenate([[0], np.cumsum(cnt)[:-1]]).astype(np.int64))
 
@@ -255,14 +288,15 @@ class EgoSequenceSplit:
         return self.image_table is not None
 
     def image_feats(self, index: torch.Tensor, generator: Optional[torch.Generator] = None, draws=None) -> torch.Tensor:
-        """[B,2048] float32: the features of ONE frame per item, drawn uniformly from the item's frames on every access
+        """[B,2048] float32 (or, with the backbone, uint8 [B,224,224,3]): the features / the crop of ONE frame per item, drawn uniformly from the item's frames on every access
         (``np.random.randint(0, number_of_images)``, dataset.py:1657-1660; here floor(u n) from `generator` on the device).
         `draws` = u [B] in [0,1) injects the random numbers."""
         dev = self.image_table.device
         cnt, off = self.image_cnt.index_select(0, index), self.image_off.index_select(0, index)
         u = draws.to(dev) if draws is not None else torch.rand(index.shape[0], device=dev, generator=generator)
         pick = torch.minimum((u.double() * cnt.double()).long(), cnt - 1) + off
-        return self.image_table.index_select(0, self.image_rows.index_select(0, pick)).float()
+        out = self.image_table.index_select(0, self.image_rows.index_select(0, pick))
+        return out if out.dtype == torch.uint8 else out.float()          # crops stay uint8 NHWC (the backbone normalises them)
 
     def scenes(self, index: torch.Tensor, generator: Optional[torch.Generator] = None, draws=None) -> torch.Tensor:
         """The scene clouds of a batch of items, in the frame the reference hands to the model.
@@ -312,7 +346,8 @@ class EgoDataModule:
     def __init__(self, root: str, dataset: str = "egobody", condition: Sequence[str] = ("text", "interactee"),
                  motion_length: int = 60, predict_transl: bool = True, device="cuda", storage: str = "device",
                  scene_root: Optional[str] = None, pose_estimation_task: bool = False, splits: Sequence[str] = ("train", "val", "test"),
-                 max_items: Optional[int] = None, interactee_pred: bool = False, scene_points: int = 20000, seed: int = 1234):
+                 max_items: Optional[int] = None, interactee_pred: bool = False, scene_points: int = 20000, seed: int = 1234,
+                 image_backbone: bool = False):
         if storage not in ("device", "pinned"):
             raise ValueError("storage: 'device' (split resident in HBM) or 'pinned' (pinned host memory, async copies)")
         self.name, self.device, self.storage = dataset, torch.device(device), storage
@@ -326,7 +361,7 @@ class EgoDataModule:
             if os.path.isdir(d):
                 pred = os.path.join(root, f"interactee_pred_{sp}.pkl") if interactee_pred else None
                 s = EgoSequenceSplit(root, sp, dataset, condition, motion_length, "angle", predict_transl, pose_estimation_task,
-                                     scene_root, max_items, pred, scene_points)
+                                     scene_root, max_items, pred, scene_points, image_backbone)
                 self.splits[sp] = s.to(self.device, pinned=(storage == "pinned"))
         if not self.splits:
             raise FileNotFoundError(f"no split directory under {root}")

@@ -19,8 +19,9 @@ What runs where
   * Only the live flows are implemented; the reference's dead code (``forward`` calling the undefined
     ``feats2joints``, t2m_eval, the ``save_for_edo`` debug dump -- SURVEY.md App. D) is not reproduced:
     ``forward``/``sample`` = what ``ego_eval`` really does (condition -> reverse diffusion -> decode).
-  * The image condition takes the ResNet-50 backbone's pooled features [B,2048] in the batch's image slot (the backbone is out of
-    scope); ``output_images`` is trainable and its stage-2 forward / gradient are glue problems, evaluation projects with a torch op.
+  * The image condition takes the ResNet-50 backbone's pooled features [B,2048] in the batch's image slot or, with
+    ``model.image_backbone``, the crops themselves (the backbone then runs here, frozen and in eval mode: seeme_amd/resnet.py);
+    ``output_images`` is trainable and its stage-2 forward / gradient are glue problems, evaluation projects with a torch op.
   * Deliberate, documented deviations from the reference: none by default, except where the reference cannot
     run as written (the image branches of ``ego_eval``: batch layout, guidance).  ``TEST.SAMPLE_MEAN``
     (condition on the posterior mean instead of a sample) and ``TEST.CFG_SCENE_ORDER: fixed`` (classifier-free guidance
@@ -39,6 +40,7 @@ from . import geometry as G
 from .config import instantiate_from_config
 from .denoiser_autograd import denoiser_forward_torch
 from .hyp_metrics import K_MAX, HypothesisMetrics, best_index, hyp_metrics_hip, keep_mask
+from .resnet import ResNet50
 from .respointnet import ResnetPointnet
 from .smpl import SMPL
 
@@ -251,7 +253,8 @@ class SyntheticEgoDataModule:
 
     def batch(self, B, idx=0, with_scene=False, lengths=None, pose_estimation=False, split="train", with_image=False):
         """with_image: pooled image features [B,2048] (non-negative, as after the backbone's final ReLU + pooling) in the image
-        layouts (motion, transl, beta, utils, [scene], images, length)."""
+        layouts (motion, transl, beta, utils, [scene], images, length); with_image="crops": seeded smooth uint8 crops
+        [B,224,224,3] instead (what EgoDataModule hands over with the backbone on)."""
         g = torch.Generator().manual_seed(self.seed * 7919 + idx)
         T = self.T
         motion = 0.5 * torch.randn(B, T, 2, self.pose_dim, generator=g)
@@ -268,7 +271,15 @@ class SyntheticEgoDataModule:
                 raise NotImplementedError("the image layouts carry no interactee ground truth (dataset.py:1788-1792)")
             # (a generator of its own: the other tensors stay those of the same idx without images)
             gi = torch.Generator().manual_seed(self.seed * 7919 + idx + 104729)
-            out.append(torch.rand(B, IMAGE_FEAT_DIM, generator=gi).pow(2).to(dev))
+            if isinstance(with_image, str):
+                if with_image != "crops":
+                    raise ValueError("with_image: False, True (pooled features) or 'crops' (uint8 crops)")
+                # bilinear upsampling of 7x7 uniform noise: smooth, full 0..255 range
+                low = torch.rand(B, 3, 7, 7, generator=gi)
+                up = torch.nn.functional.interpolate(low, size=(224, 224), mode="bilinear", align_corners=False)
+                out.append((up * 255.0).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous().to(dev))
+            else:
+                out.append(torch.rand(B, IMAGE_FEAT_DIM, generator=gi).pow(2).to(dev))
             out.append(length.to(dev))
             return tuple(out)
         out.append(length.to(dev))
@@ -282,14 +293,21 @@ class SyntheticEgoDataModule:
 
 # ----------------------------------------------------------------------------- the model
 class _SceneEncoderHolder(nn.Module):
-    """``proscene.scene_enc`` -- only this sub-module of ProHMRScene is on the path (prohmr_scene.py:102-104)."""
+    """``proscene`` -- the sub-modules of ProHMRScene on the path: ``scene_enc`` (prohmr_scene.py:102-104) for a scene condition and,
+    with ``model.image_backbone``, the ResNet-50 ``backbone`` (prohmr_scene.py:33-34, 99-100) for an image condition."""
 
-    def __init__(self):
+    def __init__(self, scene: bool = True, backbone: bool = False):
         super().__init__()
-        self.scene_enc = ResnetPointnet(512, 256)
+        if scene:
+            self.scene_enc = ResnetPointnet(512, 256)
+        if backbone:
+            self.backbone = ResNet50()
 
     def encode_scene(self, scene):
         return self.scene_enc(scene)
+
+    def encode_image(self, images):
+        return self.backbone(images)
 
 
 class MLD(nn.Module):
@@ -343,13 +361,19 @@ class MLD(nn.Module):
 
         self.vae_type = cfg.model.get("vae_type", None) or \
             cfg.model.motion_vae.target.split(".")[-1].lower().replace("vae", "")      # mld.py:174-179
+        # model.image_backbone: the frozen ResNet-50 (proscene.backbone) runs here and the image slot may hold crops; without it
+        # batches carry its pooled [B,2048] features
+        self.image_backbone = bool(cfg.model.get("image_backbone", False)) and "image" in self.condition
         if "image" in self.condition:                                     # mld.py:251-255; trainable in stage 2
-            # the ResNet-50 backbone (proscene.encode_image) stays outside: batches carry its pooled [B,2048] features
             self.output_images = nn.Sequential(nn.ReLU(), nn.Linear(IMAGE_FEAT_DIM, 256))
-        if "scene" in self.condition:                                     # mld.py:182-207, 257-261
-            self.proscene = _SceneEncoderHolder()
+        if "scene" in self.condition or self.image_backbone:              # mld.py:182-207, 257-261
+            self.proscene = _SceneEncoderHolder(scene="scene" in self.condition, backbone=self.image_backbone)
             for p in self.proscene.parameters():
                 p.requires_grad = False
+        if self.image_backbone:
+            # frozen, always eval; TRAIN.IMAGE_PRECISION bf16 runs bf16 weights and activations
+            self.proscene.backbone.precision = cfg.TRAIN.get("IMAGE_PRECISION", self.proscene.backbone.precision)
+        if "scene" in self.condition:
             # frozen scene encoder: TRAIN.SCENE_PRECISION bf16 runs the fused bf16-MFMA PointNet blocks
             self.proscene.scene_enc.precision = cfg.TRAIN.get("SCENE_PRECISION", self.proscene.scene_enc.precision)
             self.output_scene = nn.Sequential(nn.ReLU(), nn.Linear(512, 256))
@@ -416,14 +440,18 @@ class MLD(nn.Module):
         # output_scene = ReLU + Linear(512,256) (trainable, mld.py:257-261): torch op so that autograd sees it
         return self.output_scene(s512).unsqueeze(0)                       # [1,B,256]
 
-    @staticmethod
-    def _image_feats(images) -> torch.Tensor:
-        """The image slot of a batch: pooled backbone features [B,2048] (what proscene.encode_image returns, mld.py:895-896)."""
+    def _image_feats(self, images) -> torch.Tensor:
+        """The image slot of a batch -> pooled backbone features [B,2048] (what proscene.encode_image returns, mld.py:895-896):
+        features pass through; with model.image_backbone crops (float32 NCHW [B,3,224,224] normalised, or uint8 NHWC
+        [B,224,224,3] RGB) run through the HIP ResNet-50, once per sequence."""
         if not torch.is_tensor(images):
             raise TypeError(f"the image slot of the batch holds {type(images).__name__}: expected pooled image features [B,{IMAGE_FEAT_DIM}]")
+        if images.dim() == 4 and self.image_backbone:
+            with torch.no_grad():
+                return self.proscene.encode_image(images)
         if images.dim() == 4:
             raise NotImplementedError(f"the image slot holds images {tuple(images.shape)}: the ResNet-50 backbone (proscene.encode_image) "
-                                      f"is outside this path -- pass its pooled features [B,{IMAGE_FEAT_DIM}] (INTEGRATION.md)")
+                                      f"is off -- set model.image_backbone: true, or pass its pooled features [B,{IMAGE_FEAT_DIM}] (INTEGRATION.md)")
         if images.dim() != 2 or images.shape[1] != IMAGE_FEAT_DIM or not images.is_floating_point():
             raise ValueError(f"image features are {tuple(images.shape)} {images.dtype}: expected float [B,{IMAGE_FEAT_DIM}]")
         return images.float()

@@ -46,6 +46,49 @@ def recipe_tensor(key: str, shape: Tuple[int, ...], seed: int = 1234) -> np.ndar
     return np.ascontiguousarray(out, dtype=np.float32)
 
 
+def is_backbone_key(key: str) -> bool:
+    """Entries of the ResNet-50 image backbone inside a larger model (``proscene.backbone.*``)."""
+    return key.startswith("backbone.") or ".backbone." in key
+
+
+def backbone_recipe_tensor(key: str, shape: Tuple[int, ...], seed: int = 1234) -> np.ndarray:
+    """Recipe of the ResNet-50 backbone, keyed by the entry's name inside the backbone (``layer1.0.bn3.weight``; a
+    ``...backbone.`` prefix is dropped, so the module alone and the module inside MLD receive the same values).  The generic
+    recipe gives BatchNorm gains of ~0.05 and negative running variances; here convolutions are N(0, sqrt(2 / fan_in)),
+    BatchNorm weight 1 + 0.1 N (times 0.35 for every bn3 and downsample.1, which keeps the residual stream O(1) over 16 blocks),
+    bias 0.05 N, running_mean 0.1 N, running_var U(0.5, 1.5)."""
+    tail = key.split("backbone.", 1)[1] if is_backbone_key(key) else key
+    rng = np.random.Generator(np.random.PCG64(_key_seed(seed, "backbone." + tail)))
+    shape = tuple(int(s) for s in shape)
+    parts = tail.split(".")
+    leaf = parts[-1]
+    block_end = parts[-2:-1] == ["bn3"] or parts[-3:-1] == ["downsample", "1"]
+    if len(shape) == 4:
+        out = rng.standard_normal(shape) * np.sqrt(2.0 / float(np.prod(shape[1:])))
+    elif leaf == "weight":
+        out = (1.0 + 0.1 * rng.standard_normal(shape)) * (0.35 if block_end else 1.0)
+    elif leaf == "bias":
+        out = 0.05 * rng.standard_normal(shape)
+    elif leaf == "running_mean":
+        out = 0.1 * rng.standard_normal(shape)
+    elif leaf == "running_var":
+        out = 0.5 + rng.random(shape)
+    else:
+        raise KeyError(f"no backbone recipe for {key}")
+    return np.ascontiguousarray(out, dtype=np.float32)
+
+
+def load_backbone_recipe_(module, seed: int = 1234):
+    """In-place: the backbone recipe for every floating-point entry of a ResNet-50 module on its own."""
+    import torch
+
+    sd = module.state_dict()
+    new = {k: (torch.from_numpy(backbone_recipe_tensor(k, tuple(v.shape), seed)).to(dtype=v.dtype) if torch.is_floating_point(v) else v)
+           for k, v in sd.items()}
+    module.load_state_dict(new, strict=True)
+    return module
+
+
 def recipe_state_dict(shapes: Mapping[str, Iterable[int]], seed: int = 1234) -> Dict[str, np.ndarray]:
     """Fill every entry of ``{name: shape}`` by the recipe."""
     return {k: recipe_tensor(k, tuple(v), seed) for k, v in sorted(shapes.items())}
@@ -61,6 +104,7 @@ def load_recipe_(module, seed: int = 1234):
         if not torch.is_floating_point(v):
             new[k] = v
             continue
-        new[k] = torch.from_numpy(recipe_tensor(k, tuple(v.shape), seed)).to(dtype=v.dtype)
+        make = backbone_recipe_tensor if is_backbone_key(k) else recipe_tensor
+        new[k] = torch.from_numpy(make(k, tuple(v.shape), seed)).to(dtype=v.dtype)
     module.load_state_dict(new, strict=True)
     return module
