@@ -78,8 +78,9 @@ typedef struct {
     const float *norm_w, *norm_b;        /* stack-final LayerNorm */
 } SeemeSkipStack;
 
-/* fp16 copies of the VAE matrices packed in MFMA fragment order (see SeemePointnetBf16 for the layout; N padded to
- * 16, K padded to 32): the throughput mode of the VAE (fp16 MFMA operands, fp32 accumulation / residual stream). */
+/* fp16 copies of the VAE matrices packed in MFMA fragment order (N padded to 16, K padded to 32),
+ * Wp[(t * (K/32) + k/32) * 64 + lane][8] = W[16*t + (lane&15)][32*(k/32) + 8*(lane>>4) .. +7] for n-tile t:
+ * the throughput mode of the VAE (fp16 MFMA operands, fp32 accumulation / residual stream). */
 typedef struct { const uint16_t *in_w, *out_w, *l1_w, *l2_w; } SeemeXfLayerH;
 typedef struct {
     SeemeXfLayerH enc[SEEME_NLAYERS], dec[SEEME_NLAYERS];
@@ -328,22 +329,15 @@ size_t seeme_pointnet_workspace_bytes(int B, int P);
 int seeme_pointnet_encode(const SeemePointnetWeights* w, const float* points, int B, int P, float* out,
                           void* workspace, size_t ws_bytes, void* stream);
 
-/* bf16-MFMA variant (fp32 accumulation): the same weights as bf16 copies packed in MFMA fragment order,
- * Wp[((t * (K/32) + k/32) * 64 + lane][8] = W[row(t, lane&15)][32*(k/32) + 8*(lane>>4) .. +7] for n-tile t, with
- * the rows of an n-tile interleaved so that a lane of the kernel owns 16 consecutive output features:
- * row(t, q) = 64*(t/4) + 16*(q/4) + 4*(t%4) + q%4.
- * One fused persistent kernel per ResnetBlockFC on 128-point tiles, max-pool folded into the epilogue.  Results
- * differ from the fp32 path by bf16 rounding of weights and activations (tolerance stated in the tests). */
+/* bf16-MFMA variant (fp32 accumulation): the same weights as bf16 copies packed in MFMA fragment order.
+ * One fused persistent kernel per ResnetBlockFC on 256-point tiles, max-pool folded into the epilogue.  Results
+ * differ from the fp32 path by bf16 rounding of weights and activations (tolerance stated in the tests).
+ * Every member is required: a NULL one is an error. */
 typedef struct {
-    const uint16_t* fc0[4];     /* block_i.fc_0.weight   [256,512] packed */
-    const uint16_t* fc1[4];     /* block_i.fc_1.weight   [256,256] packed */
-    const uint16_t* sc[4];      /* block_i.shortcut.weight [256,512] packed (sc[0] unused: see sc3) */
     const uint16_t* posf;       /* fc_pos_0 (weight [512,3], bias) as split-bf16 operands of v_mfma_f32_16x16x16_bf16,
                                  * w = hi + lo: [32 n-tiles][64 lanes][4], lane = 16*kq + q for column 16*t + q:
                                  * kq 0: whx why whz whx | kq 1: why whz wlx wly | kq 2: wlz bh bl 0 | kq 3: 0 */
-    const float* sc3;           /* block_0.shortcut folded through fc_pos_0 (both linear, no bias: respointnet.py:35,84,93):
-                                 * [256][4] fp32 = ( Ws Wp | Ws bp ) */
-    /* Second-generation block kernels (csrc/pointnet_v2.hip; used when stream[0] != NULL): per block ONE weight stream of
+    /* Block kernels (csrc/pointnet_bf16.hip): per block ONE weight stream of
      * 24 slots x 16 fragments x 64 lanes x 8 bf16, in the order a 256-point tile consumes it.  Fragment (feature tile nt,
      * k-block kb): lane 16*kq + m, element j = W[16 nt + m][32 kb + 16 (j/4) + 4 kq + j%4] -- the k order in which an
      * accumulator tile pair is the next B operand; the activations between blocks are stored in that order too.
@@ -352,7 +346,8 @@ typedef struct {
      *   block_1-3: slots 0..7 fc_0[:, :256] k-block = slot, fragment nt; slot 8 + 8 g + kb: fragments 0..7 shortcut[:, :256]
      *              tiles 8 g + n, fragments 8..15 fc_1 tiles 8 g + n, both k-block kb. */
     const uint16_t* stream[4];
-    const uint16_t* sc3f;       /* sc3 as split-bf16 fragments like posf: [16 n-tiles][64 lanes][4] */
+    const uint16_t* sc3f;       /* block_0.shortcut folded through fc_pos_0 (both linear, no bias: respointnet.py:35,84,93) to
+                                 * [256][4] = ( Ws Wp | Ws bp ), as split-bf16 fragments like posf: [16 n-tiles][64 lanes][4] */
 } SeemePointnetBf16;
 size_t seeme_pointnet_bf16_workspace_bytes(int B, int P);
 int seeme_pointnet_encode_bf16(const SeemePointnetWeights* w, const SeemePointnetBf16* wb, const float* points,

@@ -1,4 +1,4 @@
-"""PointNet bf16 encode: time and error of the block-kernel generation selected by SEEME_PN_V2 (1 default, 0 = first generation)."""
+"""PointNet bf16 encode (B=64 x 20 000 points by default): time, and error against the fp32 path on four scenes."""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -23,5 +23,5 @@ with torch.no_grad():
     torch.cuda.synchronize()
     ms = float(np.median([a.elapsed_time(b) for a, b in ev]))
 flops = B * P * (2 * 3 * 512 + (2 * 512 * 256 + 2 * 256 * 256 + 2 * 4 * 256) + 3 * (3 * 2 * 256 * 256))
-print(json.dumps({"v2": os.environ.get("SEEME_PN_V2", "1"), "B": B, "P": P, "ms": round(ms, 4), "tflops_executed": round(flops / ms / 1e9, 1),
+print(json.dumps({"B": B, "P": P, "ms": round(ms, 4), "tflops_executed": round(flops / ms / 1e9, 1),
                   "rel_err_vs_fp32_B4": err}))

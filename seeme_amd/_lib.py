@@ -104,7 +104,7 @@ class PointnetWeights(C.Structure):
 
 
 class PointnetBf16(C.Structure):
-    _fields_ = [("fc0", fp * 4), ("fc1", fp * 4), ("sc", fp * 4), ("posf", fp), ("sc3", fp), ("stream", fp * 4), ("sc3f", fp)]
+    _fields_ = [("posf", fp), ("stream", fp * 4), ("sc3f", fp)]
 
 
 class GlueRows(C.Structure):

@@ -5,12 +5,17 @@ mld/models/modeltype/mld.py:911-922).  Same parameter names (``fc_pos_0``, ``blo
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
 
 from . import _lib as L
 from .mld_vae import _param_fingerprint
+
+
+# what _weights() builds for one parameter fingerprint: the two ABI structs and the tensors their pointers refer to
+_PackedWeights = namedtuple("_PackedWeights", "fingerprint w wb tensors")
 
 
 class _ResnetBlockFCParams(nn.Module):
@@ -40,8 +45,8 @@ class ResnetPointnet(nn.Module):
 
     def _weights(self):
         fpnt = _param_fingerprint(self)
-        if self._wcache is not None and self._wcache[0] == fpnt:
-            return self._wcache[1]
+        if self._wcache is not None and self._wcache.fingerprint == fpnt:
+            return self._wcache.w
         for p in self.parameters():
             L.require_cuda(p, "ResnetPointnet parameter")
         with torch.no_grad():
@@ -58,40 +63,36 @@ class ResnetPointnet(nn.Module):
         w.fcc_w, w.fcc_b = L.ptr(self.fc_c.weight), L.ptr(self.fc_c.bias)
         with torch.no_grad():
             bf = [getattr(self, f"block_{i}") for i in range(4)]
-            # rows of n-tile t interleaved so that a kernel lane owns 16 consecutive features (include/seeme_hip.h)
-            tt, qq = torch.meshgrid(torch.arange(16), torch.arange(16), indexing="ij")
-            perm = (64 * (tt // 4) + 16 * (qq // 4) + 4 * (tt % 4) + qq % 4).reshape(-1).to(posw.device)
-            def pack(W):   # [N,K] -> MFMA fragment order [N/16][K/32][kq=4][r=16][8] (1 KiB per wave-load)
-                N, K = W.shape
-                return W[perm].to(torch.bfloat16).view(N // 16, 16, K // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous()
-            fc0 = [pack(b.fc_0.weight) for b in bf]
-            fc1 = [pack(b.fc_1.weight) for b in bf]
-            sc = [pack(b.shortcut.weight) for b in bf]
             # block_0's shortcut acts on fc_pos_0(p): two linear maps, folded in fp64 to a 3 -> 256 map
             ws0 = bf[0].shortcut.weight.double()
             sc3 = torch.cat([ws0 @ self.fc_pos_0.weight.double(), (ws0 @ self.fc_pos_0.bias.double())[:, None]], dim=1).float().contiguous()
-            # fc_pos_0 as split-bf16 matrix-core operands (include/seeme_hip.h: SeemePointnetBf16.posf)
-            pw, pbias = self.fc_pos_0.weight.float(), self.fc_pos_0.bias.float()
-            wh, bh = pw.to(torch.bfloat16), pbias.to(torch.bfloat16)
-            wl, bl = (pw - wh.float()).to(torch.bfloat16), (pbias - bh.float()).to(torch.bfloat16)
-            zz = torch.zeros_like(bh)
-            frag = torch.stack([torch.stack([wh[:, 0], wh[:, 1], wh[:, 2], wh[:, 0]], -1),
-                                torch.stack([wh[:, 1], wh[:, 2], wl[:, 0], wl[:, 1]], -1),
-                                torch.stack([wl[:, 2], bh, bl, zz], -1),
-                                torch.stack([zz, zz, zz, zz], -1)], dim=1)             # [512, kq, 4]
-            posf = frag.view(32, 16, 4, 4).permute(0, 2, 1, 3).contiguous()            # [n-tile][kq][q][4]
-            streams, sc3f = self._pack_streams(bf, sc3, perm)
+            posf = self._split_frags(self.fc_pos_0.weight.float(), self.fc_pos_0.bias.float())
+            streams, sc3f = self._pack_streams(bf, sc3)
         wb = L.PointnetBf16()
         for i in range(4):
-            wb.fc0[i], wb.fc1[i], wb.sc[i] = fc0[i].data_ptr(), fc1[i].data_ptr(), sc[i].data_ptr()
             wb.stream[i] = streams[i].data_ptr()
-        wb.sc3, wb.posf, wb.sc3f = sc3.data_ptr(), posf.data_ptr(), sc3f.data_ptr()
-        self._wcache = (fpnt, w, (posw, fc0, fc1, sc, sc3, posf, streams, sc3f), wb)
+        wb.posf, wb.sc3f = posf.data_ptr(), sc3f.data_ptr()
+        # the structs hold raw pointers: the tensors they point into stay alive with them
+        self._wcache = _PackedWeights(fpnt, w, wb, (posw, posf, streams, sc3f))
         return w
 
     @staticmethod
-    def _pack_streams(bf, sc3, perm):
-        """Weight streams of the second-generation block kernel (include/seeme_hip.h: SeemePointnetBf16.stream): per block
+    def _split_frags(W3, bias):
+        """A 3 -> N map (W3 [N, 3], bias [N]) as split-bf16 matrix-core operands, v = hi + lo (include/seeme_hip.h:
+        SeemePointnetBf16.posf): [N/16 n-tiles][kq][q][4], k slots per kq 0: whx why whz whx | 1: why whz wlx wly |
+        2: wlz bh bl 0 | 3: zeros."""
+        wh, bh = W3.to(torch.bfloat16), bias.to(torch.bfloat16)
+        wl, bl = (W3 - wh.float()).to(torch.bfloat16), (bias - bh.float()).to(torch.bfloat16)
+        zz = torch.zeros_like(bh)
+        frag = torch.stack([torch.stack([wh[:, 0], wh[:, 1], wh[:, 2], wh[:, 0]], -1),
+                            torch.stack([wh[:, 1], wh[:, 2], wl[:, 0], wl[:, 1]], -1),
+                            torch.stack([wl[:, 2], bh, bl, zz], -1),
+                            torch.stack([zz, zz, zz, zz], -1)], dim=1)                 # [N, kq, 4]
+        return frag.view(-1, 16, 4, 4).permute(0, 2, 1, 3).contiguous()
+
+    @staticmethod
+    def _pack_streams(bf, sc3):
+        """Weight streams of the block kernel k_pn_block2 (include/seeme_hip.h: SeemePointnetBf16.stream): per block
         24 slots x 16 fragments x 64 lanes x 8 bf16 in the order a 256-point tile consumes them, and the folded block_0
         shortcut as split-bf16 fragments (sc3f)."""
         dev = sc3.device
@@ -119,17 +120,7 @@ class ResnetPointnet(nn.Module):
                               for kb in range(8)]
             assert len(slots) == 24
             streams.append(torch.stack(slots).contiguous())             # [24, 16, 64, 8] bf16
-        # sc3 [256, 4] = (Ws Wp | Ws bp); k slots as posf: kq 0: whx why whz whx | kq 1: why whz wlx wly | kq 2: wlz bh bl 0
-        sw, sbias = sc3[:, :3], sc3[:, 3]
-        wh, bh = sw.to(torch.bfloat16), sbias.to(torch.bfloat16)
-        wl, bl = (sw - wh.float()).to(torch.bfloat16), (sbias - bh.float()).to(torch.bfloat16)
-        zz = torch.zeros_like(bh)
-        fr = torch.stack([torch.stack([wh[:, 0], wh[:, 1], wh[:, 2], wh[:, 0]], -1),
-                          torch.stack([wh[:, 1], wh[:, 2], wl[:, 0], wl[:, 1]], -1),
-                          torch.stack([wl[:, 2], bh, bl, zz], -1),
-                          torch.stack([zz, zz, zz, zz], -1)], dim=1)                  # [256, kq, 4]
-        sc3f = fr.view(16, 16, 4, 4).permute(0, 2, 1, 3).contiguous()                  # [n-tile][kq][m][4]
-        return streams, sc3f
+        return streams, ResnetPointnet._split_frags(sc3[:, :3], sc3[:, 3])     # sc3 [256, 4] = (Ws Wp | Ws bp)
 
     def forward(self, p: torch.Tensor) -> torch.Tensor:
         """p [B, n_pts, 3] -> [B, out_dim]."""
@@ -147,8 +138,7 @@ class ResnetPointnet(nn.Module):
         if ev is not None:
             ev[0].record()
         if bf16:
-            wb = self._wcache[3]
-            L.check(L.lib().seeme_pointnet_encode_bf16(C.byref(w), C.byref(wb), p.data_ptr(), B, P, out.data_ptr(),
+            L.check(L.lib().seeme_pointnet_encode_bf16(C.byref(w), C.byref(self._wcache.wb), p.data_ptr(), B, P, out.data_ptr(),
                                                         self._ws.data_ptr(), self._ws.numel(), L.current_stream()),
                     "seeme_pointnet_encode_bf16")
         else:

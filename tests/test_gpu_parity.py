@@ -632,7 +632,7 @@ def test_fused_adamw_matches_torch(dev):
 
 
 def test_pointnet_bf16_tile_walk(dev):
-    """The persistent block kernels give every workgroup a contiguous range of 64-point tiles that may span scene
+    """The persistent block kernels give every workgroup a contiguous range of 256-point tiles that may span scene
     boundaries, with the column max carried in registers between tiles.  Per-point arithmetic and the max are
     independent of that partition, so a scene encoded alone (one tile per workgroup) and inside a large batch (several
     tiles per workgroup, scene changes inside a range, partial last tiles) must agree BIT-exactly; the fp32 path bounds

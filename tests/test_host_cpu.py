@@ -31,6 +31,28 @@ def test_library_exports_every_declared_symbol():
     assert lib.seeme_version() >= 100
 
 
+def test_pointnet_bf16_struct_mirrors_header():
+    """SeemePointnetBf16 holds nothing but pointers, so member names, order and array lengths are its whole layout: the
+    ctypes mirror has to repeat the header exactly (a mismatch would first show up as a wild pointer on the GPU)."""
+    from seeme_amd import _lib
+    hdr = open(os.path.join(REPO, "include", "seeme_hip.h")).read()
+    m = re.search(r"typedef struct \{((?:(?!typedef struct).)*?)\}\s*SeemePointnetBf16;", hdr, re.S)
+    assert m, "SeemePointnetBf16 not found in include/seeme_hip.h"
+    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
+    decls = [d.strip() for d in body.split(";") if d.strip()]
+    members = []
+    for d in decls:
+        mm = re.fullmatch(r"const\s+(?:uint16_t|float)\s*\*\s*(\w+)(?:\[(\d+)\])?", d)
+        assert mm, f"unexpected member declaration: {d!r}"
+        members.append((mm.group(1), int(mm.group(2)) if mm.group(2) else None))
+    assert members == [("posf", None), ("stream", 4), ("sc3f", None)]
+    mirror = [(name, ctype._length_ if issubclass(ctype, C.Array) else None) for name, ctype in _lib.PointnetBf16._fields_]
+    assert mirror == members
+    for _, ctype in _lib.PointnetBf16._fields_:
+        assert (ctype._type_ if issubclass(ctype, C.Array) else ctype) is C.c_void_p
+    assert C.sizeof(_lib.PointnetBf16) == 6 * C.sizeof(C.c_void_p)
+
+
 def test_den_layout_is_consistent():
     from seeme_amd import _lib
     n = 155
@@ -287,7 +309,7 @@ def test_smpl_pkl_loader_is_code_free(tmp_path):
 
 # ----------------------------------------------------------------------------- PointNet v2: packing of the weight streams
 def test_pointnet_v2_stream_packing_emulated():
-    """The second-generation PointNet block kernels (csrc/pointnet_v2.hip) consume host-packed weight streams whose k order
+    """The PointNet block kernels (csrc/pointnet_bf16.hip) consume host-packed weight streams whose k order
     encodes the kernel's register layouts (accumulator tile pair -> next B operand), and keep the activations between
     blocks in that fragment order.  This emulates the kernel's dataflow on the CPU -- MFMA semantics on the packed
     fragments, slot by slot, bf16 rounding where the kernel rounds, the activation layout of the stores / loads -- and
@@ -301,7 +323,7 @@ def test_pointnet_v2_stream_packing_emulated():
     ws0 = bf[0].shortcut.weight.double()
     sc3 = torch.cat([ws0 @ pn.fc_pos_0.weight.double(), (ws0 @ pn.fc_pos_0.bias.double())[:, None]], dim=1).float()
     with torch.no_grad():
-        streams, sc3f = pn._pack_streams(bf, sc3, None)
+        streams, sc3f = pn._pack_streams(bf, sc3)
     assert all(s.shape == (24, 16, 64, 8) for s in streams) and sc3f.shape == (16, 4, 16, 4)
     bf16 = lambda t: t.to(torch.bfloat16).float()
 
