@@ -521,6 +521,27 @@ size_t seeme_hyp_metrics_workspace_bytes(int B, int K, int T);
 int seeme_hyp_metrics(const float* jts_pred, const float* jts_ref, const int32_t* lengths, int B, int K, int T,
                       float* per_hyp, float* per_seq, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ per-frame mesh metrics (csrc/mesh_metrics.hip)
+ * Frame-level primitives of the EgoHMR tables (test_egohmr.py:463-492, 540-549): one float per frame, fp32 metres in and out, a
+ * frame whose map entry is negative is skipped and gets 0; the caller averages over the valid frames of a sequence and chunks the
+ * frames.  Map entries must be below the number of reference frames / scenes the caller holds (scene entries >= S are skipped).
+ * No atomics, fixed-order sums: bitwise reproducible, and a frame's value does not depend on the other frames of the launch.
+ *
+ * seeme_pa_mpjpe_frames: out[f] = mean over the 24 joints of |s R x + t - y|, x = j_pred[f], y = j_ref[ref_of_frame[f]], (s, R, t)
+ * the similarity transform of EgoHMR utils/pose_utils.py:11-59 (R a proper rotation: the reflection correction included).
+ * seeme_mesh_v2v_frames: out[f] = mean over the V vertices of |(v - pel_pred[f]) - (v_ref - pel_ref[r])|, r = ref_of_frame[f]
+ * (test_egohmr.py:485); v_pred / v_ref 16-byte aligned.
+ * seeme_scene_min_dist2: out_d2[f] = min over the V x P pairs of the SQUARED distance between verts[f] and scene[scene_of_frame[f]]:
+ * an fp32 MFMA pass in the expansion form picks the scene points that can hold the minimum (error bound in the source), those are
+ * re-evaluated in direct form; the result is the minimum over all pairs of the direct-form value.  V <= 10112 (the frame's
+ * operands live in LDS); workspace 16-byte aligned. */
+int seeme_pa_mpjpe_frames(const float* j_pred, const float* j_ref, const int32_t* ref_of_frame, int F, float* out, void* stream);
+int seeme_mesh_v2v_frames(const float* v_pred, const float* pel_pred, const float* v_ref, const float* pel_ref,
+                          const int32_t* ref_of_frame, int F, int V, float* out, void* stream);
+size_t seeme_scene_min_dist2_workspace_bytes(int F, int V, int S, int P);   /* 0 for bad sizes */
+int seeme_scene_min_dist2(const float* verts, const float* scene, const int32_t* scene_of_frame, int F, int V, int S, int P,
+                          float* out_d2, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ ResNet-50 image backbone (csrc/resnet.hip)
  * EgoHMR.models.resnet.ResNet(Bottleneck, [3,4,6,3]) without fc, frozen and in eval mode: proscene.encode_image
  * (prohmr_scene.py:99-100).  Every BatchNorm is folded on the host (float64) into its convolution:

@@ -40,6 +40,7 @@ from . import geometry as G
 from .config import instantiate_from_config
 from .denoiser_autograd import denoiser_forward_torch
 from .hyp_metrics import K_MAX, HypothesisMetrics, best_index, hyp_metrics_hip, keep_mask
+from .mesh_metrics import MeshMetrics, mesh_metrics_eval
 from .resnet import ResNet50
 from .respointnet import ResnetPointnet
 from .smpl import SMPL
@@ -337,6 +338,13 @@ class MLD(nn.Module):
             raise ValueError("TEST.CFG_SCENE_ORDER must be 'reference' or 'fixed'")
         # hypotheses per sequence in ONE evaluation pass (condition encoded once, errors and diversity per sequence): 1 = today's path
         self.num_hypotheses = self._check_num_hypotheses(cfg.TEST.get("NUM_HYPOTHESES", 1), "TEST.NUM_HYPOTHESES")
+        # PA-MPJPE, V2V and body-scene contact per hypothesis (seeme_amd/mesh_metrics.py): off = today's result, key for key
+        self.mesh_metrics = cfg.TEST.get("MESH_METRICS", False)
+        if not isinstance(self.mesh_metrics, bool):
+            raise ValueError(f"TEST.MESH_METRICS must be true or false, got {self.mesh_metrics!r}")
+        self.mesh_chunk_mb = cfg.TEST.get("MESH_CHUNK_MB", 256)
+        if isinstance(self.mesh_chunk_mb, bool) or not isinstance(self.mesh_chunk_mb, (int, float)) or not self.mesh_chunk_mb > 0:
+            raise ValueError(f"TEST.MESH_CHUNK_MB must be a positive number of MiB, got {self.mesh_chunk_mb!r}")
         self.hip_backward = cfg.TRAIN.get("HIP_BACKWARD", True)   # hand-written backward of the denoiser chain (one head)
         self.hip_vae_backward = cfg.TRAIN.get("HIP_VAE_BACKWARD", True)   # stage 1: hand-written VAE backward (vae_train.py)
         self.hip_glue = cfg.TRAIN.get("HIP_GLUE", True)           # ... and of everything around it (stage2_glue.py); needs HIP_BACKWARD
@@ -395,6 +403,7 @@ class MLD(nn.Module):
         self.losses = {k: MLDLosses(cfg) for k in ("train", "val", "test")}
         self.EgoMetric = EgoMetrics()
         self.HypMetric = HypothesisMetrics()
+        self.MeshMetric = MeshMetrics()
         self.do_classifier_free_guidance = self.guidance_scale > 1.0
         self.renorm = datamodule.renorm if datamodule is not None else (lambda x: x)
         self.times: List[float] = []
@@ -813,7 +822,16 @@ class MLD(nn.Module):
               "list_names": {}, "lat_t": z}
         if want_vertices:
             rs["vertices_ref"], rs["vertices_rst"] = out_ref[1], out_rst[1]
+        if self.mesh_metrics:
+            rs["mesh_metrics"] = self._mesh_metrics(f_rst, f_ref, b_ref, o_rst, lengths, 1, scene)
         return rs
+
+    def _mesh_metrics(self, f_rst, f_ref, b_ref, orient, lengths, K, scene):
+        """TEST.MESH_METRICS: PA_MPJPE, V2V [B,K] and, with a scene in the batch, SCENE_DIST, CONTACT_RATIO [B,K] and their _REF
+        forms [B] (seeme_amd.mesh_metrics.mesh_metrics_eval: posed and measured in chunks of TEST.MESH_CHUNK_MB MiB of vertices)."""
+        pose = lambda feats, betas, o: self._feats_to_joints(feats, betas, True, orient=o)
+        return mesh_metrics_eval(pose, f_rst, f_ref, b_ref, orient, lengths, K, scene=scene, chunk_mb=self.mesh_chunk_mb,
+                                 num_vertices=int(self.smpl_model.v_template.shape[0]))
 
     # ------------------------------------------------------------------ K hypotheses per sequence in one pass
     MAX_SAMPLE_ROWS = 512          # the largest sampling batch that has a cluster plan (one CU per sample above it)
@@ -977,6 +995,8 @@ class MLD(nn.Module):
               "orientation_quat_int": quat(f_int_r), "joints_interactee_gt": joints_int_gt, "lengths": lengths,
               "list_names": {}, "lat_t": z.view(1, B, K, -1)[:, :, 0].contiguous(),
               "joints_rst_all": joints_all, "m_rst_all": f_rst.view(B, K, min_len, -1), "lat_t_all": z, "hyp_metrics": hm}
+        if self.mesh_metrics:
+            rs["mesh_metrics"] = self._mesh_metrics(f_rst, f_ref, b_ref, o_ref, lengths, K, scene)
         if want_vertices:                                                   # meshes of hypothesis 0 only (6890 vertices per frame)
             rs["vertices_ref"] = out_ref[1]
             rs["vertices_rst"] = self._feats_to_joints(f_rst0, b_ref, True, orient=o_ref)[1]
@@ -1008,6 +1028,15 @@ class MLD(nn.Module):
                 if split != "test":
                     hm["best_index"] = best_index(hm["MPJPE"], keep_mask(hm, split, hm["have_quat"]))
                 self.HypMetric.update(hm, split)
+            if "mesh_metrics" in rs_set:                                   # TEST.MESH_METRICS
+                if "hyp_metrics" in rs_set:
+                    hm = rs_set["hyp_metrics"]
+                    keep = keep_mask(hm, split, hm["have_quat"])
+                else:                                                      # K = 1: the same rule on this batch's per-sequence errors
+                    q_rst, q_ref = rs_set.get("orientation_quat_rst"), rs_set.get("orientation_quat_ref")
+                    per = EgoMetrics.per_sequence(rs_set["joints_rst"], rs_set["joints_ref"], rs_set["lengths"], q_rst, q_ref)
+                    keep = keep_mask({k: v[:, None] for k, v in per.items()}, split, q_rst is not None and q_ref is not None)
+                self.MeshMetric.update(rs_set["mesh_metrics"], keep)
         if split == "test":
             return rs_set["joints_rst"]
         return loss
