@@ -304,6 +304,16 @@ int seeme_smpl_lbs(const SeemeSmplModel* m, const float* betas, const float* pos
 int seeme_smpl_joints_backward(const SeemeSmplModel* m, const float* betas, const float* pose, const float* djoints, int dj_stride,
                                float* dpose, float* dtransl, int M, void* stream);
 
+/* DATA_TYPE 'rot6d' (mld.py:703-742): the 24 posed joints [M,24,3] straight from the renormed features r6 [M,24,6] -- Gram-Schmidt
+ * per joint (order: SEEME_GEO_ROT6D_PROHMR or SEEME_GEO_ROT6D_DIFFUSION, as seeme_geometry), rest joints, kinematic chain -- in one
+ * launch; the same joints as seeme_geometry followed by seeme_smpl_lbs(pose_is_rotmat = 1).  betas [M,10] or NULL (zeros: the
+ * reference's create_beta=False call); transl [M,3] or NULL. */
+int seeme_smpl_joints_rot6d(const SeemeSmplModel* m, const float* betas, const float* r6, int order, const float* transl, int M,
+                            float* joints, void* stream);
+/* ... and their gradient w.r.t. r6 (dr6 [M,24,6]) and transl (dtransl [M,3], may be NULL): djoints [M, dj_stride >= 24, 3]. */
+int seeme_smpl_joints_rot6d_backward(const SeemeSmplModel* m, const float* betas, const float* r6, int order, const float* djoints,
+                                     int dj_stride, float* dr6, float* dtransl, int M, void* stream);
+
 /* ------------------------------------------------------------------ rotation helpers / renorm
  * mld/utils/geometry2.py: aa_to_quat :33-54, aa_to_rotmat :56-72, quat_to_rotmat :74-95,
  * rot6d_to_rotmat :98-117 ('prohmr' / 'diffusion' column order).  in [M,3|4|6] -> out [M,4] or [M,3,3]. */

@@ -136,16 +136,21 @@ def load_pretrained_vae(model, path: str) -> int:
 def build(cfg, dev, args, datamodule=None, smpl_model=None):
     from .mld import MLD, SyntheticEgoDataModule
     from .smpl import SMPL
+    from .shapes import motion_layout
+    data_type = str(cfg.DATA_TYPE)
     nfeats = 75 if cfg.DATASET_NAME == "egobody" else (69 if cfg.DATASET_NAME == "gimo" else cfg.model.nfeats)
+    if data_type != "angle":                                          # rot6d: 144 on EgoBody; raises for GIMO
+        nfeats = motion_layout(cfg.DATASET_NAME, data_type, True, cfg.model.nfeats)[0]
     if datamodule is None and getattr(args, "data_root", None):
         from .data import EgoDataModule
         datamodule = EgoDataModule(args.data_root, cfg.DATASET_NAME, tuple(cfg.model.condition), motion_length=int(cfg.MOTION_LENGTH),
                                    predict_transl=bool(cfg.TRAIN.ABLATION.PREDICT_TRANSL), device=dev, storage=args.storage,
                                    scene_root=args.scene_root, pose_estimation_task=bool(cfg.TEST.get("POSE_ESTIMATION_TASK", False)),
                                    interactee_pred=bool(cfg.TEST.get("INTERACTEE_PRED", False)),      # get_data.py:196
-                                   seed=int(cfg.SEED_VALUE), image_backbone=bool(cfg.model.get("image_backbone", False)))
+                                   seed=int(cfg.SEED_VALUE), image_backbone=bool(cfg.model.get("image_backbone", False)),
+                                   data_type=data_type)
     dm = datamodule or SyntheticEgoDataModule(nfeats=nfeats, T=args.frames, n_points=args.scene_points,
-                                               seed=int(cfg.SEED_VALUE), device=dev)
+                                               seed=int(cfg.SEED_VALUE), device=dev, data_type=data_type)
     if smpl_model is None and not os.path.exists(str(cfg.model.smpl_path)):
         smpl_model = SMPL.synthetic(int(cfg.SEED_VALUE))              # SMPL_NEUTRAL.pkl is licence-gated
     model = MLD(cfg, dm, smpl_model=smpl_model)

@@ -15,6 +15,7 @@ asynchronously.
 On-disk layout (what the reference reads; the datasets themselves are licence-gated and absent):
 
     <root>/mean.npy, <root>/std.npy                 [1, >= numdims + 3]: global orientation | body pose | ... translation
+    <root>/mean_rot6d.npy, <root>/std_rot6d.npy     [1, >= 144] (DATA_TYPE rot6d, EgoBody): global orientation 6 | body pose 138
     <root>/<split>/<name>.npy                       one pickled dict per sequence (``np.save(path, dict)``):
         video [L] frame names, recording_utils {original_imgname [L], fx, cx, cy [L], center [L,2], scale [L]},
         wearer / interactee {global_orient [L,1,3], transl [L,1,3], body_pose [L,1,69 | 63], betas [L,1,10]}
@@ -51,6 +52,7 @@ import numpy as np
 import torch
 
 from . import geometry as G
+from .shapes import motion_layout
 
 ADD_TRANS = np.array([[1.0, 0, 0, 0], [0, -1, 0, 0], [0, 0, -1, 0], [0, 0, 0, 1]])      # dataset.py:1195-1197
 
@@ -94,16 +96,28 @@ class EgoSequenceSplit:
     def __init__(self, root: str, split: str, dataset: str = "egobody", condition: Sequence[str] = ("text", "interactee"),
                  motion_length: int = 60, data_type: str = "angle", predict_transl: bool = True,
                  pose_estimation_task: bool = False, scene_root: Optional[str] = None, max_items: Optional[int] = None,
-                 interactee_pred: Optional[str] = None, scene_points: int = 20000, image_backbone: bool = False):
-        if data_type != "angle":
-            raise NotImplementedError("data module: DATA_TYPE 'angle' (the rot6d variant re-encodes the same files)")
-        self.dataset, self.split, self.condition = dataset, split, tuple(condition)
+                 interactee_pred: Optional[str] = None, scene_points: int = 20000, image_backbone: bool = False,
+                 encode_device=None):
+        """encode_device: where the rot6d re-encoding of the split runs (a ROCm device: seeme_amd.geometry's kernel; None or the
+        CPU: plain torch); the tensors stay on the CPU until ``to``."""
+        motion_layout("egobody" if dataset == "egobody" else "gimo", data_type, predict_transl)   # raises for an unknown DATA_TYPE and for GIMO + rot6d
+        rot6d = data_type == "rot6d"
+        self.encode_device = torch.device(encode_device) if encode_device is not None else torch.device("cpu")
+        self.dataset, self.split, self.condition, self.data_type = dataset, split, tuple(condition), data_type
         self.motion_length, self.predict_transl = int(motion_length), bool(predict_transl)
         self.pose_estimation_task = bool(pose_estimation_task)
-        self.numdims, self.go_dims = (72, 3) if dataset == "egobody" else (66, 3)          # dataset.py:1087-1088, 1828-1829
+        # the FILES hold axis-angle in both cases: (numdims, go_dims) of the stored pose, dataset.py:1087-1088, 1828-1829; rot6d
+        # (numdims 144, go_dims 6, :1094-1096) re-encodes the assembled split below
+        self.numdims, self.go_dims = (72, 3) if dataset == "egobody" else (66, 3)
         self.pose_dim = self.numdims - self.go_dims                                          # 69 | 63
-        self.mean = np.load(os.path.join(root, "mean.npy"), allow_pickle=False).astype(np.float32)
-        self.std = np.load(os.path.join(root, "std.npy"), allow_pickle=False).astype(np.float32)
+        stats = ("mean_rot6d.npy", "std_rot6d.npy") if rot6d else ("mean.npy", "std.npy")
+        for fn in stats:
+            if not os.path.exists(os.path.join(root, fn)):
+                raise FileNotFoundError(f"DATA_TYPE '{data_type}': {os.path.join(root, fn)} is missing")
+        self.mean = np.load(os.path.join(root, stats[0]), allow_pickle=False).astype(np.float32)
+        self.std = np.load(os.path.join(root, stats[1]), allow_pickle=False).astype(np.float32)
+        if rot6d and (self.mean.ndim != 2 or self.mean.shape[1] < 144 or self.std.shape != self.mean.shape):
+            raise ValueError(f"{stats[0]} / {stats[1]}: expected [1, >= 144], got {self.mean.shape} / {self.std.shape}")
         d = os.path.join(root, "test" if (dataset == "gimo" and split == "val") else split)   # GIMO has no val split (:1842-1843)
         names = sorted(n for n in os.listdir(d) if n.endswith(".npy"))
         if max_items is not None:
@@ -126,7 +140,8 @@ class EgoSequenceSplit:
         pe_motion = np.zeros((N, T, 1, self.numdims), np.float32) if pe else None
         pe_beta = np.zeros((N, T, 1, 10), np.float32) if pe else None
         first_image: List[str] = []
-        m, s = self.mean[0], self.std[0]
+        # rot6d: the split is assembled RAW (axis-angle, zero padded) and converted + normalised once, after the loop
+        m, s = (np.zeros(75, np.float32), np.ones(75, np.float32)) if rot6d else (self.mean[0], self.std[0])
         t_lo = self.numdims if dataset == "egobody" else m.shape[0] - 3                    # EgoBody: [numdims, +3); GIMO: the last three (:1607-1612, 2360-2364)
         for i, name in enumerate(names):
             it = load_pickled(os.path.join(d, name))
@@ -158,7 +173,7 @@ class EgoSequenceSplit:
                 # zero padding comes BEFORE the normalisation, as in the reference (:1524-1546): padded frames are -mean/std
                 motion[i, :, p, : self.go_dims] = (go - m[: self.go_dims]) / s[: self.go_dims]
                 motion[i, :, p, self.go_dims:] = (bp - m[self.go_dims: self.numdims]) / s[self.go_dims: self.numdims]
-                if self.predict_transl:
+                if self.predict_transl and not rot6d:                                          # 'angle' only (:1615)
                     tr = (tr - m[t_lo: t_lo + 3]) / s[t_lo: t_lo + 3]
                 transl[i, p] = tr
                 beta[i, p, :L] = bt
@@ -167,6 +182,11 @@ class EgoSequenceSplit:
         self.motion, self.transl, self.beta = torch.from_numpy(motion), torch.from_numpy(transl), torch.from_numpy(beta)
         self.utils, self.length = torch.from_numpy(utils), torch.from_numpy(length)
         self.pe_motion = torch.from_numpy(pe_motion) if pe else None
+        if rot6d:
+            self.numdims, self.go_dims, self.pose_dim = 144, 6, 138
+            self.motion = self._to_rot6d(self.motion)
+            if pe:
+                self.pe_motion = self._to_rot6d(self.pe_motion)
         self.pe_beta = torch.from_numpy(pe_beta) if pe else None
         self.scene_table = self.scene_index = self.scene_xform = self.scene_flat = self.scene_off = self.scene_cnt = None
         if "scene" in self.condition:
@@ -180,6 +200,22 @@ class EgoSequenceSplit:
                 self._load_image_crops(os.path.join(root, f"image_crops_{split}.npy"), os.path.join(root, f"image_crop_names_{split}.npy"))
             else:
                 self._load_image_feats(os.path.join(root, f"image_feats_{split}.npz"))
+
+    def _to_rot6d(self, aa: torch.Tensor) -> torch.Tensor:
+        """Raw axis-angle [N,T,P,72] = [global orientation 3 | body pose 69] -> normalised rot6d [N,T,P,144] = [go 6 | body 138]:
+        aa_to_rotmat -- seeme_amd.geometry's kernel when the split is bound for a ROCm device, plain torch on the CPU -- then the first two columns in
+        the 'diffusion' element order [r00, r01, r10, r11, r20, r21] (utils_egobody/geometry.py:256-262), zeros in the frames past
+        the sequence's length (the reference converts first, dataset.py:1376-1416, and zero-pads the converted values, :1524-1546),
+        then (x - mean) / std."""
+        flat = aa.reshape(-1, 3).float().contiguous()
+        if self.encode_device.type == "cuda":
+            R = torch.cat([G.aa_to_rotmat(c.to(self.encode_device)).cpu() for c in flat.split(1 << 22)])   # 48 MB of axis-angle at a time
+        else:
+            R = G.aa_to_rotmat_torch(flat)
+        r6 = G.rotmat_to_rot6d(R, "diffusion").reshape(*aa.shape[:-1], 144)
+        valid = torch.arange(aa.shape[1])[None, :] < self.length.reshape(-1, 1)               # [N,T]
+        r6 = r6 * valid[:, :, None, None].to(r6.dtype)
+        return ((r6 - torch.from_numpy(self.mean[0, :144])) / torch.from_numpy(self.std[0, :144])).contiguous()
 
     def _load_image_feats(self, path: str):
         """The feature table of the split and, per sequence, the table rows of its frames (flat, with offsets and counts)."""
@@ -347,12 +383,14 @@ class EgoDataModule:
                  motion_length: int = 60, predict_transl: bool = True, device="cuda", storage: str = "device",
                  scene_root: Optional[str] = None, pose_estimation_task: bool = False, splits: Sequence[str] = ("train", "val", "test"),
                  max_items: Optional[int] = None, interactee_pred: bool = False, scene_points: int = 20000, seed: int = 1234,
-                 image_backbone: bool = False):
+                 image_backbone: bool = False, data_type: str = "angle"):
         if storage not in ("device", "pinned"):
             raise ValueError("storage: 'device' (split resident in HBM) or 'pinned' (pinned host memory, async copies)")
         self.name, self.device, self.storage = dataset, torch.device(device), storage
         self.njoints = 23 if dataset == "egobody" else 21
-        self.numdims = (75 if predict_transl else 72) if dataset == "egobody" else (69 if predict_transl else 66)   # EgoBody.py:128, Gimo.py:119
+        # EgoBody.py:128, Gimo.py:119; rot6d: 24 x 6, the translation stays raw and outside (dataset.py:1094-1096, 1615)
+        self.numdims = motion_layout("egobody" if dataset == "egobody" else "gimo", data_type, predict_transl)[0]
+        self.data_type = data_type
         self.nfeats = self.numdims
         self.is_mm = False
         self.splits: Dict[str, EgoSequenceSplit] = {}
@@ -360,8 +398,8 @@ class EgoDataModule:
             d = os.path.join(root, "test" if (dataset == "gimo" and sp == "val") else sp)
             if os.path.isdir(d):
                 pred = os.path.join(root, f"interactee_pred_{sp}.pkl") if interactee_pred else None
-                s = EgoSequenceSplit(root, sp, dataset, condition, motion_length, "angle", predict_transl, pose_estimation_task,
-                                     scene_root, max_items, pred, scene_points, image_backbone)
+                s = EgoSequenceSplit(root, sp, dataset, condition, motion_length, data_type, predict_transl, pose_estimation_task,
+                                     scene_root, max_items, pred, scene_points, image_backbone, encode_device=self.device)
                 self.splits[sp] = s.to(self.device, pinned=(storage == "pinned"))
         if not self.splits:
             raise FileNotFoundError(f"no split directory under {root}")

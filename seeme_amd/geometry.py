@@ -66,3 +66,30 @@ def renorm(features: torch.Tensor, mean: torch.Tensor, std: torch.Tensor) -> tor
     s = std.reshape(-1)[:F].to(features.device, torch.float32).contiguous()
     out = _Renorm.apply(f2, m, s) if (f2.requires_grad and torch.is_grad_enabled()) else _renorm_launch(f2, m, s)
     return out.reshape(features.shape)
+
+
+def rotmat_to_rot6d(R: torch.Tensor, mode: str = "diffusion") -> torch.Tensor:
+    """[..., 3, 3] rotation matrices -> [M, 6]: the first two columns (utils_egobody/geometry.py:256-262).  'diffusion' (the
+    dataset's default): ``R[:, :, :2].reshape(-1, 6)`` = [r00, r01, r10, r11, r20, r21]; 'prohmr': the two columns one after the
+    other, [r00, r10, r20, r01, r11, r21] -- the order ``rot6d_to_rotmat`` reads under the same name.  Pure indexing, any device."""
+    if mode not in ("prohmr", "diffusion"):
+        raise ValueError(mode)
+    R = R.reshape(-1, 3, 3)
+    if mode == "diffusion":
+        return R[:, :, :2].reshape(-1, 6)
+    return R[:, :, :2].permute(0, 2, 1).reshape(-1, 6)
+
+
+def aa_to_rotmat_torch(theta: torch.Tensor) -> torch.Tensor:
+    """``aa_to_rotmat`` in plain torch (any device and dtype; the data module's conversion on the CPU): axis-angle [M,3] ->
+    quaternion with the half angle of ||theta + 1e-8|| -> [M,3,3], the formulas of the kernel (geometry2.py:33-95)."""
+    theta = theta.reshape(-1, 3)
+    ang = torch.norm(theta + 1e-8, dim=1, keepdim=True)
+    q = torch.cat([torch.cos(0.5 * ang), torch.sin(0.5 * ang) * (theta / ang)], dim=1)
+    q = q / q.norm(dim=1, keepdim=True)
+    w, x, y, z = q.unbind(1)
+    w2, x2, y2, z2 = w * w, x * x, y * y, z * z
+    wx, wy, wz, xy, xz, yz = w * x, w * y, w * z, x * y, x * z, y * z
+    return torch.stack([w2 + x2 - y2 - z2, 2 * xy - 2 * wz, 2 * wy + 2 * xz,
+                        2 * wz + 2 * xy, w2 - x2 + y2 - z2, 2 * yz - 2 * wx,
+                        2 * xz - 2 * wy, 2 * wx + 2 * yz, w2 - x2 - y2 + z2], dim=1).view(-1, 3, 3)

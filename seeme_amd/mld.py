@@ -43,6 +43,7 @@ from .hyp_metrics import K_MAX, HypothesisMetrics, best_index, hyp_metrics_hip, 
 from .mesh_metrics import MeshMetrics, mesh_metrics_eval
 from .resnet import ResNet50
 from .respointnet import ResnetPointnet
+from .shapes import motion_layout
 from .smpl import SMPL
 
 
@@ -235,9 +236,21 @@ class SyntheticEgoDataModule:
     """Batches with the EgoBody/GIMO tuple layout (mld/data/humanml/data/dataset.py:1754-1794, 2479-2509): motion
     [B,T,2,72 | 66], transl [B,2,T,3], beta [B,2,T,10], utils [B,T,6], scene [B,P,3], length [B,1]; mean/std
     for ``renorm`` (mld/data/EgoBody.py:151-157).  Datasets are licence-gated, so this is what tests and
-    benchmarks run on."""
+    benchmarks run on.
 
-    def __init__(self, nfeats=75, T=196, n_points=2048, seed=1234, device="cpu", pose_dim=None):
+    data_type "rot6d" (EgoBody only, nfeats 144): motion [B,T,2,144] whose RENORMED values are the rot6d encoding of random
+    rotations -- axis-angle draws -> rotation matrices -> the first two columns in the order the model reads
+    (``geometry.rot6d_to_rotmat``'s default), then the inverse of ``renorm`` -- so that training on these batches stays away from
+    degenerate Gram-Schmidt inputs; the translation stays raw and outside the features."""
+
+    def __init__(self, nfeats=75, T=196, n_points=2048, seed=1234, device="cpu", pose_dim=None, data_type="angle"):
+        if data_type not in ("angle", "rot6d"):
+            raise ValueError(f"data_type must be 'angle' or 'rot6d', got {data_type!r}")
+        self.data_type = data_type
+        if data_type == "rot6d":
+            if nfeats != 144 or pose_dim not in (None, 144):
+                raise ValueError(f"data_type 'rot6d' is 24 joints x 6 = 144 features (nfeats {nfeats}, pose_dim {pose_dim})")
+            pose_dim = 144
         self.nfeats, self.T, self.n_points = nfeats, T, n_points
         # per-person pose width of `motion`: EgoBody 72 (24 joints, axis-angle), GIMO 66 (root + 21 joints); the VAE sees
         # pose + 3 translation values = nfeats when TRAIN.ABLATION.PREDICT_TRANSL (mld.py:121-123)
@@ -258,7 +271,10 @@ class SyntheticEgoDataModule:
         [B,224,224,3] instead (what EgoDataModule hands over with the backbone on)."""
         g = torch.Generator().manual_seed(self.seed * 7919 + idx)
         T = self.T
-        motion = 0.5 * torch.randn(B, T, 2, self.pose_dim, generator=g)
+        rot6d = self.data_type == "rot6d"
+        motion = 0.5 * torch.randn(B, T, 2, 72 if rot6d else self.pose_dim, generator=g)
+        if rot6d:
+            aa, motion = motion, self._encode_rot6d(motion)
         transl = torch.randn(B, 2, T, 3, generator=g)
         beta = 0.5 * torch.randn(B, 2, 1, 10, generator=g).expand(B, 2, T, 10).contiguous()
         utils_ = torch.zeros(B, T, 6)
@@ -287,9 +303,17 @@ class SyntheticEgoDataModule:
         if with_scene and not pose_estimation:
             out.append([])          # img_path / dict_images slot
         if pose_estimation:         # interactee ground truth: motion [B,T,1,72], transl [B,1,T,3], beta [B,T,1,10] (mld.py:1119-1131)
-            noise = 0.05 * torch.randn(B, T, self.pose_dim, generator=g)
-            out += [(motion[:, :, 1] + noise).unsqueeze(2).to(dev), transl[:, 1:2].clone().to(dev), beta[:, 1].unsqueeze(2).to(dev)]
+            if rot6d:
+                gt = self._encode_rot6d(aa[:, :, 1] + 0.05 * torch.randn(B, T, 72, generator=g))
+            else:
+                gt = motion[:, :, 1] + 0.05 * torch.randn(B, T, self.pose_dim, generator=g)
+            out += [gt.unsqueeze(2).to(dev), transl[:, 1:2].clone().to(dev), beta[:, 1].unsqueeze(2).to(dev)]
         return tuple(out)
+
+    def _encode_rot6d(self, aa):
+        """axis-angle [..., 72] (CPU) -> normalised rot6d features [..., 144]: (encoding - mean) / std, the inverse of renorm."""
+        r6 = G.rotmat_to_rot6d(G.aa_to_rotmat_torch(aa.reshape(-1, 3)), "prohmr").reshape(*aa.shape[:-1], 144)
+        return (r6 - self.mean[0, :144].cpu()) / self.std[0, :144].cpu()
 
 
 # ----------------------------------------------------------------------------- the model
@@ -349,12 +373,8 @@ class MLD(nn.Module):
         self.hip_vae_backward = cfg.TRAIN.get("HIP_VAE_BACKWARD", True)   # stage 1: hand-written VAE backward (vae_train.py)
         self.hip_glue = cfg.TRAIN.get("HIP_GLUE", True)           # ... and of everything around it (stage2_glue.py); needs HIP_BACKWARD
         self.pose_estimation_task = cfg.TEST.get("POSE_ESTIMATION_TASK", False)      # mld.py:116
-        if self.name_dataset == "egobody":                               # mld.py:122-125
-            self.nfeats = 75 if self.predict_transl else 72
-        elif self.name_dataset == "gimo":
-            self.nfeats = 69 if self.predict_transl else 66
-        else:
-            self.nfeats = cfg.model.nfeats
+        # mld.py:122-125; rot6d: 24 x 6 features, the translation outside them whatever PREDICT_TRANSL says, EgoBody only
+        self.nfeats, self.transl_in_feats = motion_layout(self.name_dataset, self.data_type, self.predict_transl, cfg.model.nfeats)
         if "image" in self.condition and self.pose_estimation_task:
             raise NotImplementedError("TEST.POSE_ESTIMATION_TASK with an 'image' condition: the reference's dataset returns no interactee "
                                       "ground truth in the image batch layouts (dataset.py:1788-1792)")
@@ -471,11 +491,11 @@ class MLD(nn.Module):
 
     def _wearer_features(self, feats_ref, transl, idx):
         f = feats_ref[:, :, idx, :]
-        if self.predict_transl:
+        if self.transl_in_feats:
             f = torch.cat([f, transl[:, idx, :, :]], dim=-1)
         if f.shape[-1] != self.vae.nfeats:
             raise ValueError(f"motion features are {f.shape[-1]} wide (pose {feats_ref.shape[-1]}"
-                             f"{' + 3 translation' if self.predict_transl else ''}) but the VAE was built with nfeats "
+                             f"{' + 3 translation' if self.transl_in_feats else ''}) but the VAE was built with nfeats "
                              f"{self.vae.nfeats} (model.nfeats)")
         return f.contiguous()
 
@@ -675,7 +695,10 @@ class MLD(nn.Module):
             z = dist_m.rsample() if eps is None else mu + eps.to(mu) * std
             m_rst = self.renorm(dec(z, lengths))                           # differentiable (geometry._Renorm)
             with torch.no_grad():
-                joints_ref = self._feats_to_joints(m_ref, beta[:, idx])[:, :, :nj]
+                if self.data_type == "rot6d" and m_ref.is_cuda:            # one fused launch (seeme_smpl_joints_rot6d)
+                    joints_ref = self._rot6d_joints(m_ref, hip=True)
+                else:
+                    joints_ref = self._feats_to_joints(m_ref, beta[:, idx])[:, :, :nj]
             joints_rst = self._feats_to_joints_torch(m_rst, beta[:, idx], orient=ref_orient)[:, :, :nj]
         else:
             z, dist_m = self._sample_latent(f_ref, lengths, eps)
@@ -715,10 +738,11 @@ class MLD(nn.Module):
         return joints
 
     def _feats_to_joints_torch(self, feats, betas, orient=None):
-        """Differentiable version of _feats_to_joints for stage-1 training ('angle' data: axis-angle pose)."""
+        """Differentiable version of _feats_to_joints for stage-1 training.  'rot6d' (mld.py:703-742): the first 144 features, zero
+        betas, no translation, `orient` ignored."""
         from .vae_autograd import smpl_joints_torch
-        if self.data_type != "angle":
-            raise NotImplementedError("stage-1 training twin: DATA_TYPE 'angle'")
+        if self.data_type == "rot6d":
+            return self._rot6d_joints(feats, hip=self.hip_vae_backward and feats.is_cuda)
         B, T, _ = feats.shape
         nb = 69 if self.name_dataset == "egobody" else 63
         pose = feats[:, :, :3 + nb]
@@ -732,6 +756,17 @@ class MLD(nn.Module):
             from .smpl import smpl_joints_hip
             return smpl_joints_hip(self.smpl_model, betas.reshape(-1, 10).float(), pose.float(), tr).reshape(B, T, 24, 3)
         return smpl_joints_torch(self.smpl_model, betas.reshape(-1, 10).float(), pose.float(), tr).reshape(B, T, 24, 3)
+
+    def _rot6d_joints(self, feats, hip: bool):
+        """[B,T,24,3] joints of renormed rot6d features [B,T,>=144] (model-side element order, zero betas, no translation),
+        differentiable: the fused HIP forward / hand-written backward (smpl._JointsRot6d) or the autograd twin."""
+        B, T, _ = feats.shape
+        r6 = feats[:, :, :144].reshape(B * T, 24, 6).float()
+        if hip:
+            from .smpl import smpl_joints_rot6d_hip
+            return smpl_joints_rot6d_hip(self.smpl_model, None, r6, None).reshape(B, T, 24, 3)
+        from .vae_autograd import smpl_joints_rot6d_torch
+        return smpl_joints_rot6d_torch(self.smpl_model, None, r6, None).reshape(B, T, 24, 3)
 
     # ------------------------------------------------------------------ evaluation (mld.py:1076-1905, live part)
     @torch.no_grad()
@@ -808,7 +843,7 @@ class MLD(nn.Module):
         if int_gt is not None:              # mld.py:1843-1866: SMPL joints of the interactee's ground-truth motion
             g_motion, g_transl, _g_beta = int_gt
             f_gt = g_motion[:, :min_len, 0]
-            if self.predict_transl:
+            if self.transl_in_feats:
                 f_gt = torch.cat([f_gt, g_transl[:, 0, :min_len]], dim=-1)
             joints_int_gt = self._feats_to_joints(self.renorm(f_gt.contiguous()), beta[:, 1, :min_len])
         if self.data_type == "angle":
@@ -967,7 +1002,7 @@ class MLD(nn.Module):
         if int_gt is not None:
             g_motion, g_transl, _g_beta = int_gt
             f_gt = g_motion[:, :min_len, 0]
-            if self.predict_transl:
+            if self.transl_in_feats:
                 f_gt = torch.cat([f_gt, g_transl[:, 0, :min_len]], dim=-1)
             joints_int_gt = self._feats_to_joints(self.renorm(f_gt.contiguous()), beta[:, 1, :min_len])
         if self.data_type == "angle":

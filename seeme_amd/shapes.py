@@ -97,3 +97,25 @@ def pointnet_shapes(out_dim: int = 512, hidden: int = 256) -> Shapes:
         _lin(f"block_{i}.shortcut.", s, hidden, 2 * hidden, bias=False)
     _lin("fc_c.", s, out_dim, hidden)
     return s
+
+
+def motion_layout(dataset: str, data_type: str, predict_transl: bool, nfeats: int = 0) -> Tuple[int, bool]:
+    """(width of the VAE's motion features, whether the translation is part of them) -- the one statement of the rule
+    (reference mld.py:100-123, dataset.py:1087-1096, 1615, 1828-1834).  'angle': EgoBody 72, GIMO 66, + 3 with
+    TRAIN.ABLATION.PREDICT_TRANSL; any other dataset name: `nfeats` as configured.  'rot6d': EgoBody only, 24 x 6 = 144 and the
+    translation stays outside whatever PREDICT_TRANSL says; GIMO's rot6d features are 22 x 6 = 132 wide while the model's rot6d
+    branch reshapes to 24 joints (mld.py:709-717), so that combination raises, as it cannot run in the reference either."""
+    if data_type not in ("angle", "rot6d"):
+        raise ValueError(f"DATA_TYPE must be 'angle' or 'rot6d', got {data_type!r}")
+    if data_type == "rot6d":
+        if dataset == "gimo":
+            raise NotImplementedError("DATA_TYPE 'rot6d' with GIMO: its features are 22 x 6 = 132 wide (dataset.py:1832-1834) while the "
+                                      "model's rot6d branch reshapes to 24 joints (mld.py:709-717); the reference cannot run that "
+                                      "combination either")
+        return (144 if dataset == "egobody" else int(nfeats)), False
+    t = 3 if predict_transl else 0
+    if dataset == "egobody":
+        return 72 + t, bool(predict_transl)
+    if dataset == "gimo":
+        return 66 + t, bool(predict_transl)
+    return int(nfeats), bool(predict_transl)

@@ -259,3 +259,54 @@ def smpl_joints_hip(smpl, betas: torch.Tensor, pose_aa: torch.Tensor, transl: to
     """[M,24,3] posed joints, differentiable w.r.t. pose_aa [M,72] and transl [M,3] (HIP forward and backward)."""
     L.require_cuda(pose_aa, "pose_aa")
     return _JointsAA.apply(smpl, betas, pose_aa, transl)
+
+
+_ROT6D_ORDER = {"prohmr": L.GEO_ROT6D_PROHMR, "diffusion": L.GEO_ROT6D_DIFFUSION}
+
+
+class _JointsRot6d(torch.autograd.Function):
+    """The 24 posed joints as a differentiable function of the rot6d pose [M,24,6] and the translation [M,3]: forward =
+    ``seeme_smpl_joints_rot6d`` (Gram-Schmidt + kinematic chain in one launch), backward = ``seeme_smpl_joints_rot6d_backward``
+    (the tree walk of ``seeme_smpl_joints_backward`` followed by the Gram-Schmidt backward; the joints loss of the rot6d branch of
+    ``train_vae_forward``, mld.py:703-742).  betas (None = zeros) get no gradient."""
+
+    @staticmethod
+    def forward(ctx, smpl, betas, r6, transl, order):
+        M = r6.shape[0]
+        r6 = r6.to(torch.float32).reshape(M, 24, 6).contiguous()
+        betas = None if betas is None else betas.to(torch.float32).reshape(M, 10).contiguous()
+        tr = None if transl is None else transl.to(torch.float32).reshape(M, 3).contiguous()
+        joints = torch.empty(M, 24, 3, device=r6.device, dtype=torch.float32)
+        model = smpl._model()
+        L.check(L.lib().seeme_smpl_joints_rot6d(C.byref(model), L.ptr(betas), r6.data_ptr(), order, L.ptr(tr), M, joints.data_ptr(),
+                                                L.current_stream()), "seeme_smpl_joints_rot6d")
+        ctx.smpl, ctx.has_tr, ctx.has_betas, ctx.order = smpl, tr is not None, betas is not None, order
+        ctx.save_for_backward(r6, *([betas] if betas is not None else []))
+        return joints
+
+    @staticmethod
+    def backward(ctx, dj):
+        r6 = ctx.saved_tensors[0]
+        betas = ctx.saved_tensors[1] if ctx.has_betas else None
+        M = r6.shape[0]
+        dj = dj.to(torch.float32).contiguous()
+        dr6 = torch.empty_like(r6)
+        dtr = torch.empty(M, 3, device=r6.device, dtype=torch.float32) if ctx.has_tr else None
+        model = ctx.smpl._model()
+        L.check(L.lib().seeme_smpl_joints_rot6d_backward(C.byref(model), L.ptr(betas), r6.data_ptr(), ctx.order, dj.data_ptr(), 24,
+                                                         dr6.data_ptr(), L.ptr(dtr), M, L.current_stream()),
+                "seeme_smpl_joints_rot6d_backward")
+        return None, None, dr6, dtr, None
+
+
+def smpl_joints_rot6d_hip(smpl, betas: Optional[torch.Tensor], r6: torch.Tensor, transl: Optional[torch.Tensor] = None,
+                          order: str = "prohmr") -> torch.Tensor:
+    """[M,24,3] posed joints from the rot6d pose r6 [M,24,6] (or [M,144]), differentiable w.r.t. r6 and transl [M,3] (HIP forward
+    and backward).  betas [M,10] or None (zeros); order: the element order ``geometry.rot6d_to_rotmat`` reads ('prohmr' default)."""
+    if order not in _ROT6D_ORDER:
+        raise ValueError(f"order must be 'prohmr' or 'diffusion', got {order!r}")
+    L.require_cuda(r6, "r6")
+    if r6.numel() != r6.shape[0] * 144:
+        raise ValueError(f"r6 is {tuple(r6.shape)}: expected [M,24,6] or [M,144]")
+    # (the Function sees [M,24,6] whatever the caller's form: its backward returns that shape, autograd reshapes it back)
+    return _JointsRot6d.apply(smpl, betas, r6.reshape(r6.shape[0], 24, 6), transl, _ROT6D_ORDER[order])

@@ -137,17 +137,17 @@ def _rodrigues(aa: torch.Tensor) -> torch.Tensor:
     return eye + s * K + (1 - c) * (K @ K)
 
 
-def smpl_joints_torch(smpl, betas: torch.Tensor, pose_aa: torch.Tensor, transl: torch.Tensor = None) -> torch.Tensor:
-    """The 24 posed SMPL joints [M,24,3], differentiable w.r.t. pose and translation (betas too).
-    pose_aa [M,72] = global_orient | body_pose."""
-    M = pose_aa.shape[0]
+def _smpl_joints_from_rotmat(smpl, betas, R: torch.Tensor, transl: torch.Tensor = None) -> torch.Tensor:
+    """Posed joints [M,24,3] from local rotation matrices R [M,24,3,3] in R's dtype (float64 included); betas [M,10] or None."""
+    M = R.shape[0]
     # rest joints = J_regressor (v_template + shapedirs betas), with the regressor folded in (SURVEY.md App. E7)
     cache = getattr(smpl, "_joint_fold", None)
-    if cache is None or cache[0].device != betas.device:
+    if cache is None or cache[0].device != R.device:
         cache = (smpl.J_regressor @ smpl.v_template, torch.einsum("jv,vkl->jkl", smpl.J_regressor, smpl.shapedirs))
         smpl._joint_fold = cache
-    J = cache[0][None] + torch.einsum("jkl,bl->bjk", cache[1], betas)                # [M,24,3]
-    R = _rodrigues(pose_aa.reshape(-1, 3)).view(M, 24, 3, 3)
+    J = cache[0].to(R.dtype)[None].expand(M, -1, -1)                                  # [M,24,3]
+    if betas is not None:
+        J = J + torch.einsum("jkl,bl->bjk", cache[1].to(R.dtype), betas.to(R.dtype))
     parents = smpl.parents.tolist()
     rel = J.clone()
     rel[:, 1:] = J[:, 1:] - J[:, parents[1:]]
@@ -158,3 +158,31 @@ def smpl_joints_torch(smpl, betas: torch.Tensor, pose_aa: torch.Tensor, transl: 
         chain.append(chain[parents[i]] @ Tm[:, i])
     posed = torch.stack(chain, dim=1)[:, :, :3, 3]
     return posed if transl is None else posed + transl[:, None, :]
+
+
+def smpl_joints_torch(smpl, betas: torch.Tensor, pose_aa: torch.Tensor, transl: torch.Tensor = None) -> torch.Tensor:
+    """The 24 posed SMPL joints [M,24,3], differentiable w.r.t. pose and translation (betas too).
+    pose_aa [M,72] = global_orient | body_pose."""
+    M = pose_aa.shape[0]
+    return _smpl_joints_from_rotmat(smpl, betas, _rodrigues(pose_aa.reshape(-1, 3)).view(M, 24, 3, 3), transl)
+
+
+def rot6d_to_rotmat_torch(x: torch.Tensor, rot6d_mode: str = "prohmr") -> torch.Tensor:
+    """geometry2.rot6d_to_rotmat (:98-117) in plain torch, differentiable, any dtype: x [M,6] -> [M,3,3].  'prohmr': a1 = x[0:3],
+    a2 = x[3:6]; 'diffusion': a1 = x[0::2], a2 = x[1::2].  Gram-Schmidt with F.normalize (x / max(||x||, 1e-12))."""
+    if rot6d_mode not in ("prohmr", "diffusion"):
+        raise ValueError(rot6d_mode)
+    x = x.reshape(-1, 2, 3).permute(0, 2, 1) if rot6d_mode == "prohmr" else x.reshape(-1, 3, 2)
+    a1, a2 = x[:, :, 0], x[:, :, 1]
+    b1 = F.normalize(a1, dim=1)
+    b2 = F.normalize(a2 - (b1 * a2).sum(dim=1, keepdim=True) * b1, dim=1)
+    b3 = torch.cross(b1, b2, dim=1)
+    return torch.stack((b1, b2, b3), dim=-1)
+
+
+def smpl_joints_rot6d_torch(smpl, betas, r6: torch.Tensor, transl: torch.Tensor = None, order: str = "prohmr") -> torch.Tensor:
+    """Twin of ``smpl.smpl_joints_rot6d_hip``: the 24 posed joints [M,24,3] from the rot6d pose r6 [M,24,6] (or [M,144]),
+    differentiable w.r.t. r6 and transl, in r6's dtype -- in float64 it is the oracle of the HIP kernels.  betas [M,10] or None."""
+    M = r6.shape[0]
+    R = rot6d_to_rotmat_torch(r6.reshape(-1, 6), order).view(M, 24, 3, 3)
+    return _smpl_joints_from_rotmat(smpl, betas, R, None if transl is None else transl.to(R.dtype))
