@@ -367,9 +367,12 @@ int seeme_pointnet_encode_bf16(const SeemePointnetWeights* w, const SeemePointne
  * out[out_off + n*ldo + k] = sum_b gout[b*ldg + y_col + n] * gout[b*ldg + x_col + k], n < nn <= 32, k < kk <= 256, where
  * gout is the per-sample buffer of seeme_denoiser_backward (x and dy of every linear, csrc/den_train.h).  Replaces the
  * autograd weight-gradient accumulation of loss.backward() through MldDenoiser.forward (mld.py:582-631). */
+/* (out is stored, not accumulated; elements of out outside the tiles -- the ldo - kk gap of a row included -- are not written; the sum
+ * over b runs in order in one thread: two launches give the same bits.) */
 int seeme_den_wgrad(const float* gout, int ldg, int B, const void* tiles, int n_tiles, float* out, void* stream);
 /* The chain's vector gradients (biases, LayerNorm weights / biases) in one launch: out[q] = sum_b gout[b*ldg + idx[q]], q < n,
- * and dpe_row0[c] = sum_b gout[b*ldg + dx0_col + c], c < 256 (query_pos.pe row 0; NULL to skip).  Same reference as above. */
+ * and dpe_row0[c] = sum_b gout[b*ldg + dx0_col + c], c < 256 (query_pos.pe row 0; NULL to skip the write -- the 256 columns from
+ * dx0_col are read either way and must lie inside a row).  idx may repeat.  Same reference as above. */
 int seeme_den_vecgrad(const float* gout, int ldg, int B, const int64_t* idx, int n, float* out, int dx0_col, float* dpe_row0,
                       void* stream);
 
@@ -398,7 +401,7 @@ int seeme_adamw_step_dev(const void* chunks, int n_chunks, void* const* params, 
  * self-attention K|V of the condition and time tokens, text_norm + linear-attention key|value, AdaLN scale|shift rows). */
 typedef struct {
     int B, N;                 /* samples, condition tokens per sample */
-    const float* dist;        /* [2, dist_rows, 256]: row 0 mu, row 1 logvar (seeme_vae_encode_dist); rows [0,B) = target,
+    const float* dist;        /* [2, dist_rows, 256]: row 0 mu, row 1 logvar (seeme_vae_encode_dist), z = mu + eps * exp(logvar / 2); rows [0,B) = target,
                                  rows [B,2B) = condition motion when eps_c is set */
     int dist_rows;
     const float* eps_z;       /* [B,256] rsample noise of the target */
@@ -412,18 +415,21 @@ typedef struct {
     int flip_sin_to_cos;
     float* latents;           /* [B,256] z */
     float* noisy;             /* [B,256] x_t */
-    float* tfeat;             /* [B,256] */
-} SeemeGlueRows;
+    float* tfeat;             /* [B,256]: [sin | cos](float(t) * freq[j]), the product in fp32; cos first when flip_sin_to_cos */
+} SeemeGlueRows;                 /* noisy = sqrt(acp[t]) z + sqrt(1 - acp[t]) noise.  1 <= N <= 4; with eps_c, dist_rows >= 2B. */
 int seeme_glue_rows(const SeemeGlueRows* a, void* stream);
 /* F.layer_norm(x, (256,)) without affine: xhat [M,256], rstd [M]. */
 int seeme_glue_ln(const float* x, float* xhat, float* rstd, int M, void* stream);
 
 /* One problem of seeme_grouped_gemm:  C[i,j] (+)= sum_s sum_{k < seg_len[s]} A_s[i,k] * B_s[k,j]  (+ bias[j]) (* epilogue)
  * with A_s[i,k] = pro_a(a[s][i*a_rs + k*a_ks[s]]) and B_s[k,j] = pro_b(b[s][k*b_ks[s] + j*b_cs]); prologue modes: 0 none, 1 SiLU,
- * 2 ReLU, 3 affine v*p0[idx] + p1[idx] (idx = k for A, j for B).  epi 1: multiply by SiLU'(e0[i*e_ld + j]); epi 2: by alpha.
- * colsum (needs
- * a_rs == 1): colsum[i] (+)= sum_s sum_k a[s][i,k] -- the bias gradient that comes free with a weight gradient.  tile0 /
- * tiles_n: position of the problem's 64x64 tiles in the launch. */
+ * 2 ReLU, 3 affine v*p0[idx] + p1[idx] (idx = k for A, j for B; k counts WITHIN the segment, every segment reads p0 / p1 from
+ * element 0, so they hold max seg_len entries).  epi 1: multiply by SiLU'(e0[i*e_ld + j]); epi 2: by alpha.  The order is
+ * C = ((A B + bias) * epilogue) + addend, and then the accumulate mode is applied to that value.  1 <= nseg <= 10 and every
+ * seg_len >= 1.
+ * colsum (needs a_rs == 1 and a_pro == 0): colsum[i] (+)= sum_s sum_k a[s][i,k], the raw operand -- the bias gradient that comes
+ * free with a weight gradient; it is stored / added / atomically added as `accumulate` says for C.  tile0 / tiles_n: position
+ * of the problem's 64x64 tiles in the launch (tile0 ascending over the table; a problem has nbatch * ceil(M/64) * tiles_n tiles). */
 typedef struct {
     const float* a[10];
     const float* b[10];
@@ -453,7 +459,8 @@ typedef struct {
     float alpha;              /* epi 2: C = alpha * (A B + bias) */
     const float* addend;      /* optional [M,N] (row stride add_ld) added after the epilogue */
     long add_ld;
-} SeemeGemmProblem;              /* accumulate: 0 store, 1 C += (one writer), 2 atomicAdd (nbatch members share C: split reduction) */
+} SeemeGemmProblem;              /* accumulate: 0 store, 1 C += (one writer), 2 atomicAdd (nbatch members share C: split reduction).
+                                  * Batch members may share C (c_bstride == 0) ONLY with accumulate == 2: with 0 or 1 they would race. */
 int seeme_grouped_gemm(const SeemeGemmProblem* probs_dev, int n_probs, int n_tiles, void* stream);
 int seeme_gemm_problem_bytes(void);
 /* Plain large fp32 GEMM on the matrix cores (the projections of the stage-1 training step): C[M,N] = A[M,K] B + bias[N] + addend,
@@ -495,7 +502,9 @@ typedef struct {
     float* y; float* xhat; float* rstd;
     long M; int sub_seq_rows; float eps;
 } SeemeVtLn;
-int seeme_vt_add_ln(const SeemeVtLn* a, void* stream);        /* y = LN(sub + res); keeps xhat, rstd */
+/* y = LN(sub + res) * gamma + beta over the 256 features (biased variance); keeps xhat = (v - mean) * rstd and
+ * rstd = 1 / sqrt(var + eps) for the backward.  sub_seq_rows > 0: row m reads sub[m / sub_seq_rows]. */
+int seeme_vt_add_ln(const SeemeVtLn* a, void* stream);
 typedef struct {
     const float* dy; const float* xhat; const float* rstd; const float* gamma;
     float* dpre;              /* [M,256] gradient w.r.t. (sub + res) */
@@ -503,8 +512,12 @@ typedef struct {
     long M; int accumulate;   /* 1: dpre += */
     const float* dy2;         /* optional second gradient of the same output (skip connection): dy + dy2 */
 } SeemeVtLnBwd;
+/* With d = dy (+ dy2) and g = d * gamma: dpre (+)= rstd * (g - mean(g) - xhat * mean(g * xhat)); dgamma += sum_m d * xhat and
+ * dbeta += sum_m d ALWAYS accumulate (the caller zeroes them), whatever `accumulate` says for dpre. */
 int seeme_vt_ln_bwd(const SeemeVtLnBwd* a, void* stream);
-/* scores [B,S,S] = q k^T (unscaled) -> softmax(scale * s) over the keys [0, min(S, n_prefix + lengths[b])), zeros elsewhere. */
+/* scores [B,S,S] = q k^T (unscaled) -> softmax(scale * s) over the keys [0, n_b), n_b = min(S, n_prefix + lengths[b]), exact zeros
+ * elsewhere whatever the masked inputs hold (NaN included).  1 <= S <= 512; n_b >= 1 is the caller's contract (a sequence without
+ * a valid key has no softmax: its rows would be 0/0). */
 int seeme_vt_softmax_fwd(float* scores, const int32_t* lengths, int B, int S, int n_prefix, float scale, void* stream);
 /* dp [rows,S] (gradient w.r.t. the probabilities) -> gradient w.r.t. the unscaled scores, in place. */
 int seeme_vt_softmax_bwd(float* dp, const float* p, long rows, int S, float scale, void* stream);
@@ -513,7 +526,8 @@ int seeme_vt_gelu(const float* pre, const float* dh, float* out, long n, void* s
 /* out[b,:] (+)= sum_s w[b,s] d[b,s,:]  (d [B,S,256]); w = wmask[b,s] ? scale : 0, or 1 when wmask is NULL. */
 int seeme_vt_seq_sum(const float* d, float* out, int B, int S, int accumulate, const unsigned char* wmask, float scale, void* stream);
 /* Inverted dropout with a given keep-mask (nn.Dropout / the attention-weight dropout of nn.MultiheadAttention in training,
- * cross_attention.py:264-273,324-337): out = x * mask * scale, scale = 1 / (1 - p); in place allowed; x / out 16-byte aligned, mask 4-byte aligned. */
+ * cross_attention.py:264-273,324-337): out = x * scale (one float32 rounding) where the mask byte is non-zero, +0 elsewhere; scale =
+ * 1 / (1 - p); in place allowed; x / out 16-byte aligned, mask 4-byte aligned. */
 int seeme_vt_dropout(const float* x, const unsigned char* mask, float scale, float* out, long n, void* stream);
 /* Decoder cross-attention to the single latent token under dropout (cross_attention.py:357-362):
  * out[b,s,:] = ((wmask[b,s] ? scale : 0) * cvn[b,:] + bo) * (m2[b,s,:] ? scale : 0). */
