@@ -201,45 +201,29 @@ constexpr int cl_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? h
 //   W?B  after its sweep, during the vector algebra;   W3  during the ffn epilogue
 // -- released through words in LDS, accessed through the LDS address space (through a generic pointer the compiler emits flat loads waited for
 // with vmcnt(0): seven waves spinning on those sit in the very queue the polls need).  The epilogue wave requests its eighth of a window's
-// unit BEFORE it releases the others (behind them it would wait out their backlog).  The rest (next layer's A1, B, C) goes out in phase F.
-//   units A0 A1 | B | C | D | E | F0 F1 = 0..7:  W1A D | W1B E | W2A F0 | W2B F1 | W3 next A0 | phase F: next A1 | inline in F: next B, C
+// unit BEFORE it releases the others (behind them it would wait out their backlog).  The rest (the next layer's A0, A1) goes out after phase F.
+//   units A0 A1 | B | C | D | E | F0 F1 = 0..7:  W1A B C | W1B D | W2A E | W2B F0 | W3 F1 | after F: next A0 A1
 #ifndef DCL_POLL_SLEEP
 #define DCL_POLL_SLEEP 12
 #endif
 template <int... Us> using ClSeq = std::integer_sequence<int, Us...>;
-template <int C, bool MF, bool Q> struct ClSched { static constexpr bool WIN = false; static constexpr int PRO = 0; typedef ClSeq<> W1A, W1B, W2A, W2B, WXA, WXB, W3, PF, AF; };
-#ifndef DCL_SCHED
-#define DCL_SCHED 9
-#endif
-#ifndef DCL_SCHED_C4
-#define DCL_SCHED_C4 1     // ... and for clusters of four CUs
-#endif
-#ifndef DCL_SCHED_Q
-#define DCL_SCHED_Q 1      // the windowed schedule also for two condition tokens (C = 8, 16-bit images)
-#endif
-#if DCL_SCHED == 8      // "early": every unit one window ahead of the inline scheme; the next layer's B and C still go out inline in phase F (PRO: units in flight at a layer's start)
-template <> struct ClSched<8, true, false> { static constexpr bool WIN = true; static constexpr int PRO = 4; typedef ClSeq<> WXA, WXB; typedef ClSeq<4> W1A; typedef ClSeq<5> W1B; typedef ClSeq<6> W2A; typedef ClSeq<7> W2B;
-                                             typedef ClSeq<8> W3; typedef ClSeq<9> PF; typedef ClSeq<10, 11> AF; };
-#elif DCL_SCHED == 9    // "just in time": a unit goes out in the window before the phase that consumes it; only the next layer's A is requested inline (after F)
+template <int C, bool MF, bool Q> struct ClSched { static constexpr bool WIN = false; static constexpr int PRO = 0; typedef ClSeq<> W1A, W1B, W2A, W2B, WXA, WXB, W3, AF; };
+// "Just in time": a unit goes out in the window before the phase that consumes it; only the next layer's A is requested inline (after F).
+// PRO: units in flight at a layer's start.  (Measured against it and dropped: "early", every unit one window ahead of the inline scheme, with
+// the next layer's B and C still inline in phase F; and just in time with two units in the second exchange window as well.)
 template <> struct ClSched<8, true, false> { static constexpr bool WIN = true; static constexpr int PRO = 2; typedef ClSeq<> WXA, WXB; typedef ClSeq<2, 3> W1A; typedef ClSeq<4> W1B; typedef ClSeq<5> W2A; typedef ClSeq<6> W2B;
-                                             typedef ClSeq<7> W3; typedef ClSeq<> PF; typedef ClSeq<8, 9> AF; };
-#elif DCL_SCHED == 10   // as 9, with the second exchange window taking two units as well, so that only the skip layers' A1 is left inline
-template <> struct ClSched<8, true, false> { static constexpr bool WIN = true; static constexpr int PRO = 2; typedef ClSeq<> WXA, WXB; typedef ClSeq<2, 3> W1A; typedef ClSeq<4> W1B; typedef ClSeq<5, 6> W2A; typedef ClSeq<7> W2B;
-                                             typedef ClSeq<8> W3; typedef ClSeq<> PF; typedef ClSeq<9> AF; };
-#endif
-// Two condition tokens (Q: the ca_block keeps its query G and proj_out H stages and a third exchange X3), just in time as schedule 9:
+                                             typedef ClSeq<7> W3; typedef ClSeq<8, 9> AF; };
+// Two condition tokens (Q: the ca_block keeps its query G and proj_out H stages and a third exchange X3), just in time as well:
 //   units A 0 | AS 1 | B 2 | C 3 | G 4 | H 5 6 | D 7 | E 8 | F 9 10 | (11 phantom);  ring slot = U % 4
 //   W1A B C | W1B G | W2A H0 | W2B H1 | WXA (X3 published) D | WXB (X3 swept) E | W3 (ffn epilogue) F0 F1 | after F: next A, AS
-template <> struct ClSched<8, true, true> { static constexpr bool WIN = DCL_SCHED_Q != 0; static constexpr int PRO = 2; typedef ClSeq<2, 3> W1A; typedef ClSeq<4> W1B; typedef ClSeq<5> W2A; typedef ClSeq<6> W2B;
-                                            typedef ClSeq<7> WXA; typedef ClSeq<8> WXB; typedef ClSeq<9, 10> W3; typedef ClSeq<> PF; typedef ClSeq<12, 13> AF; };
-// Four CUs per sample (16-bit images, 32 < B <= 64): units A 0 1 | AS 2 3 | B 4 5 | C 6 7 | D 8 | E 9 | F 10 11 (the table k_den_cluster_ms uses);
-// with two condition tokens: ... | G 8 | H 9 10 | D 11 | E 12 | F 13 14 | (15 phantom)
-#if DCL_SCHED_C4
+template <> struct ClSched<8, true, true> { static constexpr bool WIN = true; static constexpr int PRO = 2; typedef ClSeq<2, 3> W1A; typedef ClSeq<4> W1B; typedef ClSeq<5> W2A; typedef ClSeq<6> W2B;
+                                            typedef ClSeq<7> WXA; typedef ClSeq<8> WXB; typedef ClSeq<9, 10> W3; typedef ClSeq<12, 13> AF; };
+// Four CUs per sample (16-bit images, 32 < B <= 64): units A 0 1 | AS 2 3 | B 4 5 | C 6 7 | D 8 | E 9 | F 10 11;
+// with two condition tokens: ... | G 8 | H 9 10 | D 11 | E 12 | F 13 14 | (15 phantom).  k_den_cluster_ms runs the same tables.
 template <> struct ClSched<4, true, false> { static constexpr bool WIN = true; static constexpr int PRO = 4; typedef ClSeq<4, 5> W1A; typedef ClSeq<6, 7> W1B; typedef ClSeq<8, 9> W2A; typedef ClSeq<10, 11> W2B;
-                                             typedef ClSeq<> WXA, WXB; typedef ClSeq<12, 13> W3; typedef ClSeq<> PF; typedef ClSeq<14, 15> AF; };
+                                             typedef ClSeq<> WXA, WXB; typedef ClSeq<12, 13> W3; typedef ClSeq<14, 15> AF; };
 template <> struct ClSched<4, true, true> { static constexpr bool WIN = true; static constexpr int PRO = 4; typedef ClSeq<4, 5> W1A; typedef ClSeq<6, 7> W1B; typedef ClSeq<8, 9> W2A; typedef ClSeq<10> W2B;
-                                            typedef ClSeq<11> WXA; typedef ClSeq<12> WXB; typedef ClSeq<13, 14> W3; typedef ClSeq<> PF; typedef ClSeq<16, 17, 18, 19> AF; };
-#endif
+                                            typedef ClSeq<11> WXA; typedef ClSeq<12> WXB; typedef ClSeq<13, 14> W3; typedef ClSeq<16, 17, 18, 19> AF; };
 template <typename WT, int C, bool Q, int... Us>
 __device__ __forceinline__ void cl_issue_seq(ClRing<WT>& ring, int wave, unsigned voff, __amdgpu_buffer_rsrc_t rsrc, unsigned bc, unsigned bn,
                                              bool sc, bool sn, ClSeq<Us...>) {
@@ -896,7 +880,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
             __syncthreads(); DEN_DBG(0);
             // ================= F: ffn.proj_out.out_layers + residual (replicated); writes the next layer's input =================
             if constexpr (Q) nxt.load(4, wave, lane, vp, Ln, tt_next, ln, A, b, c, ca_next, ca_R);
-            if constexpr (WIN) cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::PF{});
+            if constexpr (WIN) __builtin_amdgcn_sched_barrier(0);   // (the fence of a window that requests nothing any more; without it stage F's first fragment reads move up)
             {
                 f32x4 acc[2];
                 cl_zero<2>(acc);

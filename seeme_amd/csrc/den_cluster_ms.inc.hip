@@ -14,7 +14,7 @@
 //   measures slower: a CU's exchange volume grows with C x samples; up to B = 64 the windowed one-sample kernel on 4 CUs is faster)
 // fp16 weight image (the bench default; two A rows per sample), one condition token (tabulated ca term) or two (template Q: query / proj_out
 // stages and a third exchange per sample), one head, no CFG, one timestep row per step: everything else stays on k_den_sample / k_den_cluster.  The weight image, the unit program and the exchange
-// protocol are k_den_cluster's (inline load schedule), results are bit-identical to it; LDS differs: the A-operand buffers hold 16 rows,
+// protocol are k_den_cluster's, results are bit-identical to it; LDS differs: the A-operand buffers hold 16 rows,
 // and the per-layer vector operands are kept in a COMPACT block (only the slices this CU reads: 2 944 floats instead of 6 272 at C = 4)
 // with the samples' K slices behind it; a sample's V' row and its tabulated ca term are read from global memory by its epilogue wave
 // right before it waits for an exchange.  109 KB (C = 4) / 98 KB (C = 8) of LDS.
@@ -30,28 +30,16 @@
                               // circle through the CU's memory queue while they wait (B = 512: 4.94 -> 4.79 ms; B = 128, two samples: 3.60 -> 3.65,
                               // and k_den_cluster at B = 32: 2.44 -> 2.6 ms -- there the successful poll IS the sweep)
 
-#ifndef DCLM_IDLE_FLAGS
-#define DCLM_IDLE_FLAGS 1     // waves without a sample request their window share behind sample 0's publish / sweep (words in LDS), not at once
-#endif
-#ifndef DCLM_PUB_ALL
-#define DCLM_PUB_ALL 1        // an epilogue wave's own window requests also wait until every sample of the CU has published
-#endif
-#ifndef DCLM_WIN
-#define DCLM_WIN 1            // 1: every unit of the weight stream is requested inside an exchange / vector-algebra window (below); 0: inline, as consumed
-#endif
-// The windowed schedule.  Requested as consumed (k_den_cluster's inline schedule) the stream is exposed time: a 1-KiB wave-request costs the CU's
+// The windowed schedule (the only one built).  Requested as consumed (k_den_cluster's inline schedule, measured here first) the stream is exposed time: a 1-KiB wave-request costs the CU's
 // address path 16+ cycles, the issuing wave waits its turn, and at 608-700 KB per layer and CU (C = 4) that is 26 k of a layer's 41 k cycles.  Here
 // every wave is busy in every phase, so there are no idle waves to do the requesting -- but every wave has dead time of its own: between
 // publishing and the first poll of an exchange, and behind its sweep.  Each wave requests ITS eighth of the coming units there:
 //   W1A after the X1 publish (stage B's units), W1B behind the X1 sweep (stage C's), W2A after the X2 publish (D, E), W2B behind its sweep (F),
 //   W3 in the ffn epilogue (next layer's A, x half), AF after stage F (next layer's A, skip half).  Ring slot of unit U = U % 4: a unit goes
 //   out only after unit U - 4 was consumed (C = 4: A 0 1 | AS 2 3 | B 4 5 | C 6 7 | D 8 | E 9 | F 10 11;  C = 8: A 0 | AS 1 | B 2 | C 3 | D 4 | E 5 | F 6 7).
-// Two condition tokens (Q): the unit tables and windows of ClSched<C, true, true> (den_cluster.inc.hip), WXA / WXB around the third exchange.
-template <int C, bool Q> struct ClmSched;
-template <> struct ClmSched<4, false> { static constexpr int PRO = 4; typedef ClSeq<4, 5> W1A; typedef ClSeq<6, 7> W1B; typedef ClSeq<8, 9> W2A; typedef ClSeq<10, 11> W2B; typedef ClSeq<> WXA, WXB; typedef ClSeq<12, 13> W3; typedef ClSeq<14, 15> AF; };
-template <> struct ClmSched<8, false> { static constexpr int PRO = 2; typedef ClSeq<2, 3> W1A; typedef ClSeq<4> W1B; typedef ClSeq<5> W2A; typedef ClSeq<6> W2B; typedef ClSeq<> WXA, WXB; typedef ClSeq<7> W3; typedef ClSeq<8, 9> AF; };
-template <> struct ClmSched<4, true> { static constexpr int PRO = 4; typedef ClSeq<4, 5> W1A; typedef ClSeq<6, 7> W1B; typedef ClSeq<8, 9> W2A; typedef ClSeq<10> W2B; typedef ClSeq<11> WXA; typedef ClSeq<12> WXB; typedef ClSeq<13, 14> W3; typedef ClSeq<16, 17, 18, 19> AF; };
-template <> struct ClmSched<8, true> { static constexpr int PRO = 2; typedef ClSeq<2, 3> W1A; typedef ClSeq<4> W1B; typedef ClSeq<5> W2A; typedef ClSeq<6> W2B; typedef ClSeq<7> WXA; typedef ClSeq<8> WXB; typedef ClSeq<9, 10> W3; typedef ClSeq<12, 13> AF; };
+// The unit tables are k_den_cluster's: ClSched<C, true, Q> (den_cluster.inc.hip); two condition tokens (Q): WXA / WXB around the third exchange.
+// Waves without a sample request their window share behind sample 0's publish / sweep (words in LDS), not at once; an epilogue wave's own
+// window requests also wait until every sample of the CU has published (both measured against the alternative: profiles/r03_g_cluster_ms.txt).
 
 // A rows per sample.  NARROW (fp16 only): two -- (hi, lo) -- so that 8 samples share the 16 rows and a lane group's accumulator rows 4 g .. 4 g + 3 hold
 // two samples; otherwise four -- fp16 (hi, lo, -, -), bf16 (hi, mid, lo, -) -- 4 samples, one per lane group (half the epilogue work per lane: the
@@ -147,12 +135,8 @@ __device__ __forceinline__ void clm_wait_published(const int* f, int target) {
     while (*(const cl_lds_flag*)f < target) __builtin_amdgcn_s_sleep(1);
 }
 __device__ __forceinline__ void clm_published(int* f, int lane, int target) {
-#if DCLM_IDLE_FLAGS
     if (lane == 0) __hip_atomic_fetch_add((__attribute__((address_space(3))) int*)f, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#if DCLM_PUB_ALL
     clm_wait_published(f, target);
-#endif
-#endif
 }
 
 // one piece (<= 1 KiB) of the NEXT layer's operands per wave and phase k = 0 .. 5: requested at the top of the phase, stored to the other
@@ -208,11 +192,7 @@ struct ClmStage {
         }
         dst = d; n4 = n;
         r = make_float4(0.f, 0.f, 0.f, 0.f);
-#ifdef DCLM_ABL_NOSTAGE   // timing-only build: the layer operands are never re-staged (wrong results)
-        if (k >= 0 && l >= 0 && lane < 0)
-#else
         if (lane < n)
-#endif
             r = *reinterpret_cast<const float4*>(src + 4 * lane);
     }
     __device__ __forceinline__ void store(int lane, float* __restrict__ stg) const {
@@ -228,11 +208,8 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster_ms(const ClArgs ka)
     constexpr int MS = M::MS;
     constexpr int N = Q ? 2 : 1;                 // condition tokens
     constexpr int NT = N + 2;                    // score slots: self, condition token(s), time
-    constexpr int A_DEF0 = cl_clamp(2 * G::TA - W::RU, 0, 2 * G::TA);
-    constexpr bool WIN = DCLM_WIN != 0;
-    static_assert(WIN || !Q, "two condition tokens: windowed schedule only");
-    constexpr int A_INL0 = WIN ? 0 : cl_clamp(A_DEF0, 0, G::TA), A_INL1 = WIN ? 0 : cl_clamp(A_DEF0 - G::TA, 0, G::TA), C_INL = WIN ? 0 : cl_clamp(G::TB - W::RU, 0, G::TB);
-    typedef ClmSched<C, Q> SCH;
+    typedef ClSched<C, true, Q> SCH;             // (every unit is requested in a window: the stages request nothing inline)
+    static_assert(SCH::WIN, "k_den_cluster_ms needs a windowed schedule table for this cluster size");
     const SeemeSampleArgs& A = ka.s;
     const DenLayout* __restrict__ lay = &ka.lay;
     const float* __restrict__ vp = ka.vp;
@@ -331,7 +308,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster_ms(const ClArgs ka)
         const unsigned bb = (unsigned)((0 * C + c) * G::NU) * W::UNIT_BYTES;
         cl_issue<WT, C, Q, 0>(ring, wave, voff, wg, bb, bb, false, false);
         cl_issue<WT, C, Q, 1>(ring, wave, voff, wg, bb, bb, false, false);
-        if constexpr (!WIN || SCH::PRO == 4) {      // (PRO = 2: units 2, 3 go out in the first X1 window)
+        if constexpr (SCH::PRO == 4) {      // (PRO = 2: units 2, 3 go out in the first X1 window)
             cl_issue<WT, C, Q, 2>(ring, wave, voff, wg, bb, bb, false, false);
             cl_issue<WT, C, Q, 3>(ring, wave, voff, wg, bb, bb, false, false);
         }
@@ -369,10 +346,10 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster_ms(const ClArgs ka)
                 f32x4 acc[G::TA];
                 cl_zero<G::TA>(acc);
                 const bool act = skip || !ywave;
-                cl_units<WT, C, Q, G::U_A, G::TA, G::TA, 0, 0, A_INL0>(ring, xa, acc, act, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, G::TA>{});
+                cl_units<WT, C, Q, G::U_A, G::TA, G::TA, 0, 0, 0>(ring, xa, acc, act, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, G::TA>{});
                 {
                     const ClX xs = clm_xin(SKF + (l == 3 ? M::XBUF : 0), lane);
-                    cl_units<WT, C, Q, G::U_AS, G::TA, G::TA, G::TA, W::UL, A_INL1>(ring, xs, acc, skip, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, G::TA>{});
+                    cl_units<WT, C, Q, G::U_AS, G::TA, G::TA, G::TA, W::UL, 0>(ring, xs, acc, skip, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, G::TA>{});
                 }
                 if (act) {
 #pragma unroll
@@ -423,7 +400,9 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster_ms(const ClArgs ka)
 #pragma unroll
                 for (int n = 0; n < N; ++n)
                     cvp[n] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_ct, (unsigned)lane * 16u, (unsigned)((n * SEEME_CROW + l * 512 + 256) * 4), 0));
-                if constexpr (WIN) { __builtin_amdgcn_sched_barrier(0); clm_published(FLG + 2, lane, pub1); cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W1A{}); }
+                __builtin_amdgcn_sched_barrier(0);
+                clm_published(FLG + 2, lane, pub1);
+                cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W1A{});
                 // ---- X1: gather v' (and y), all-reduce the scores
                 const int pub = (4 * lane) / G::S, off = (4 * lane) % G::S;
                 const unsigned o_v = (unsigned)((G::G_X1 + pub * G::X1_G + off) * 8);
@@ -460,7 +439,8 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster_ms(const ClArgs ka)
                     if (__all(ok != 0u) || dead) break;
                     if (++spins > DCL_SPIN_LIMIT) { dead = true; if (lane == 0) atomicOr(ka.hdr, 2u); break; }
                 }
-                if constexpr (WIN) { cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W1B{}); if (DCLM_IDLE_FLAGS && wave == 0 && lane == 0) cl_flag_set(FLG + 3, e1); }
+                cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W1B{});
+                if (wave == 0 && lane == 0) cl_flag_set(FLG + 3, e1);
                 DEN_DBG(0);
                 float sc[NT];
 #pragma unroll
@@ -485,22 +465,21 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster_ms(const ClArgs ka)
                 if (skip) xr = make_float4(__uint_as_float(gy0.x), __uint_as_float(gy0.z), __uint_as_float(gy1.x), __uint_as_float(gy1.z));
                 xr = wave_ln(f4_add(xr, att), VP + M::O_N1W, VP + M::O_N1B, lane);        // the "values" carry out_proj: residual + norm1
                 clm_put4<WT, NARROW>(XB, es, lane, xr);
-            } else if constexpr (WIN) {        // (waves without a sample: their eighth of both windows -- behind sample 0's publish and sweep, as in
+            } else {                           // (waves without a sample: their eighth of both windows -- behind sample 0's publish and sweep, as in
                                                //  k_den_cluster: requested at once they would stand in front of the epilogue waves' granule stores)
-                if (DCLM_IDLE_FLAGS) clm_wait_published(FLG + 2, pub1);
+                clm_wait_published(FLG + 2, pub1);
                 cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W1A{});
-                if (DCLM_IDLE_FLAGS) cl_flag_wait(FLG + 3, e1);
+                cl_flag_wait(FLG + 3, e1);
                 cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W1B{});
             }
             __syncthreads(); DEN_DBG(0);
 
             // ================= B: linear1 + ReLU, column-split =================
             nxt.load(0, wave, lane, vp, Ln, tt_next, ln, A, b0, nact, c);
-            if constexpr (!WIN) cl_refills<WT, C, Q, G::U_A + A_DEF0>(ring, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, 2 * G::TA - A_DEF0>{});   // slots of stage A
             {
                 f32x4 acc[G::TB];
                 cl_zero<G::TB>(acc);
-                cl_units<WT, C, Q, G::U_B, G::TB, G::TB, 0, 0, (WIN ? 0 : G::TB)>(ring, xb, acc, true, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, G::TB>{});
+                cl_units<WT, C, Q, G::U_B, G::TB, G::TB, 0, 0, 0>(ring, xb, acc, true, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, G::TB>{});
 #pragma unroll
                 for (int t = 0; t < G::TB; ++t) {
                     const int jh = (wave * G::TB + t) * 16 + col;
@@ -518,7 +497,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster_ms(const ClArgs ka)
             {
                 f32x4 acc[2];
                 cl_zero<2>(acc);
-                cl_units<WT, C, Q, G::U_C, G::TB, 2, 0, 0, C_INL>(ring, xh, acc, true, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, G::TB>{});
+                cl_units<WT, C, Q, G::U_C, G::TB, 2, 0, 0, 0>(ring, xh, acc, true, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, G::TB>{});
 #pragma unroll
                 for (int tt = 0; tt < 2; ++tt) {
                     const int n = (2 * wave + tt) * 16 + col;
@@ -533,7 +512,9 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster_ms(const ClArgs ka)
                 // the tabulated ca_block term of this (sample, step, layer): requested here, lands while the exchange is waited for
                 float4 cadd = make_float4(0.f, 0.f, 0.f, 0.f);
                 if constexpr (!Q) cadd = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_ca, (unsigned)lane * 16u, (unsigned)((step * SEEME_DEN_NL + l) * 1024), 0));
-                if constexpr (WIN) { __builtin_amdgcn_sched_barrier(0); clm_published(FLG + 2, lane, pub2); cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W2A{}); }
+                __builtin_amdgcn_sched_barrier(0);
+                clm_published(FLG + 2, lane, pub2);
+                cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W2A{});
                 float4 sum;
                 unsigned spins = 0;
                 if (sentinel) {   // cheap wait first: one granule per (publisher, writing wave): column 0 of the wave's first tile
@@ -566,7 +547,8 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster_ms(const ClArgs ka)
                     if (__all(ok != 0u) || dead) break;
                     if (++spins > DCL_SPIN_LIMIT) { dead = true; if (lane == 0) atomicOr(ka.hdr, 4u); break; }
                 }
-                if constexpr (WIN) { cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W2B{}); if (DCLM_IDLE_FLAGS && wave == 0 && lane == 0) cl_flag_set(FLG + 3, e2); }
+                cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W2B{});
+                if (wave == 0 && lane == 0) cl_flag_set(FLG + 3, e2);
                 DEN_DBG(0);
                 // + bias, residual, norm2, + the tabulated ca_block term (one condition token: seeme_denoiser_ca_tables)
                 xr = wave_ln(f4_add(xr, f4_add(sum, ld4(VP + M::O_L2B + 4 * lane))), VP + M::O_N2W, VP + M::O_N2B, lane);
@@ -577,10 +559,10 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster_ms(const ClArgs ka)
                     clm_put4<WT, NARROW>(XB, es, lane, wave_ln(xr, VP + M::O_CNW, VP + M::O_CNB, lane));   // ca_block.norm -> input of the query (mdiff_transformer.py:229)
                 }
                 st4(RES + es * 256 + 4 * lane, xr);
-            } else if constexpr (WIN) {
-                if (DCLM_IDLE_FLAGS) clm_wait_published(FLG + 2, pub2);
+            } else {
+                clm_wait_published(FLG + 2, pub2);
                 cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W2A{});
-                if (DCLM_IDLE_FLAGS) cl_flag_wait(FLG + 3, e2);
+                cl_flag_wait(FLG + 3, e2);
                 cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W2B{});
             }
             __syncthreads(); DEN_DBG(0);
@@ -657,7 +639,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster_ms(const ClArgs ka)
                         if (++spins > DCL_SPIN_LIMIT) { dead = true; if (lane == 0) atomicOr(ka.hdr, 8u); break; }
                     }
                     cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::WXB{});
-                    if (DCLM_IDLE_FLAGS && wave == 0 && lane == 0) cl_flag_set(FLG + 3, e3);
+                    if (wave == 0 && lane == 0) cl_flag_set(FLG + 3, e3);
                     DEN_DBG(0);
                     const float mc = __uint_as_float(g3[0].x), lc = __uint_as_float(g3[0].z);
                     float Mx = mc;
@@ -683,9 +665,9 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster_ms(const ClArgs ka)
                     const float4 hh = f4_adaln(wave_ln(y, VP + M::O_CSNW, VP + M::O_CSNB, lane), ld4(VP + M::O_CSC + 4 * lane), ld4(VP + M::O_CSH + 4 * lane));
                     clm_put4<WT, NARROW>(XB, es, lane, f4_silu(hh));
                 } else {
-                    if (DCLM_IDLE_FLAGS) clm_wait_published(FLG + 2, pub3);
+                    clm_wait_published(FLG + 2, pub3);
                     cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::WXA{});
-                    if (DCLM_IDLE_FLAGS) cl_flag_wait(FLG + 3, e3);
+                    cl_flag_wait(FLG + 3, e3);
                     cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::WXB{});
                 }
                 __syncthreads(); DEN_DBG(0);
@@ -716,11 +698,10 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster_ms(const ClArgs ka)
 
             // ================= D: ffn.linear1 + GELU (replicated) =================
             nxt.load(Q ? 3 : 1, wave, lane, vp, Ln, tt_next, ln, A, b0, nact, c);
-            if constexpr (!WIN) cl_refills<WT, C, Q, G::U_C + C_INL>(ring, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, G::TB - C_INL>{});       // slots of stage C
             {
                 f32x4 acc[1];
                 cl_zero<1>(acc);
-                cl_units<WT, C, Q, G::U_D, 1, 1, 0, 0, (WIN ? 0 : 1)>(ring, xa, acc, true, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, 1>{});
+                cl_units<WT, C, Q, G::U_D, 1, 1, 0, 0, 0>(ring, xa, acc, true, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, 1>{});
                 const int jh = wave * 16 + col;
                 const float bh = VP[M::O_F1B + jh];
 #pragma unroll
@@ -733,7 +714,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster_ms(const ClArgs ka)
             {
                 f32x4 acc[2];
                 cl_zero<2>(acc);
-                cl_units<WT, C, Q, G::U_E, 1, 2, 0, 0, (WIN ? 0 : 1)>(ring, xh, acc, true, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, 1>{});
+                cl_units<WT, C, Q, G::U_E, 1, 2, 0, 0, 0>(ring, xh, acc, true, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, 1>{});
 #pragma unroll
                 for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
@@ -741,7 +722,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster_ms(const ClArgs ka)
                         if (g2 + j < nact) PART[(g2 + j) * 256 + (2 * wave + tt) * 16 + col] = clm_out<WT, NARROW>(acc[tt], j);
             }
             __syncthreads(); DEN_DBG(0);
-            if constexpr (WIN) cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W3{});
+            cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W3{});
             if (epi) {
                 const float4 y2 = f4_add(ld4(PART + es * 256 + 4 * lane), ld4(VP + M::O_F2B + 4 * lane));
                 const float4 hh = f4_adaln(wave_ln(y2, VP + M::O_FSNW, VP + M::O_FSNB, lane), ld4(VP + M::O_TSC + 4 * lane), ld4(VP + M::O_TSH + 4 * lane));
@@ -753,8 +734,8 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster_ms(const ClArgs ka)
             {
                 f32x4 acc[2];
                 cl_zero<2>(acc);
-                cl_units<WT, C, Q, G::U_F, 2, 2, 0, 0, (WIN ? 0 : 2)>(ring, xb, acc, true, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, 2>{});
-                if constexpr (WIN) cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::AF{});
+                cl_units<WT, C, Q, G::U_F, 2, 2, 0, 0, 0>(ring, xb, acc, true, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, 2>{});
+                cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::AF{});
 #pragma unroll
                 for (int tt = 0; tt < 2; ++tt) {
                     const int n = (2 * wave + tt) * 16 + col;
@@ -772,7 +753,6 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster_ms(const ClArgs ka)
                 }
             }
             nxt.store(lane, STGN);
-            if constexpr (!WIN) cl_refills<WT, C, Q, G::NU_REAL>(ring, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, G::NU - G::NU_REAL>{});   // (phantom units)
             __syncthreads(); DEN_DBG(0);
             if (l + 1 < SEEME_DEN_NL) {
                 if (epi && !nskip) xr = ld4(RES + es * 256 + 4 * lane);               // residual of the next layer's attention

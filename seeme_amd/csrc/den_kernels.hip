@@ -169,9 +169,6 @@ __device__ __forceinline__ void den_dbg(int mode) {   // 0: stamp, 1: arm (reset
 // ---- issue: chunk C of matrix G (base = byte offset of the matrix in the image) -> ring slot
 template <typename WT, int G, int C>
 __device__ __forceinline__ void issue_mat(u32x4 (&slot)[DEN_CH], int tid, __amdgpu_buffer_rsrc_t rsrc, unsigned mat_bytes) {
-#ifdef DEN_DBG_NOLOAD   // timing probe: arithmetic and epilogues without the weight stream
-    return;
-#endif
     typedef GS<WT, G> S;
     if constexpr (WT::MFMA) {
         const unsigned voff = (unsigned)(tid >> 6) * (unsigned)(S::TW * S::KB * 1024) + (unsigned)(tid & 63) * 16u;
@@ -231,11 +228,6 @@ __device__ __forceinline__ float bf_hi(uint32_t u) { return __uint_as_float(u & 
 // acc[s][j] += W-chunk(output half j) . x[s][k0 ...]   (x in LDS, broadcast reads; packed fp32 FMAs)
 template <typename WT, int MS>
 __device__ __forceinline__ void consume(const u32x4 (&b)[DEN_CH], const float* __restrict__ x, int ldx, int k0, f2 (&acc)[MS][2][2]) {
-#ifdef DEN_DBG_NOFMA   // timing probe: keep the weight stream, drop the arithmetic (results are garbage)
-#pragma unroll
-    for (int i = 0; i < DEN_CH; ++i) acc[0][0][0].x += __uint_as_float(b[i].x ^ b[i].y ^ b[i].z ^ b[i].w);
-    return;
-#endif
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
 #pragma unroll
@@ -354,12 +346,8 @@ __device__ __forceinline__ void gemv_chunk(Ring& ring, int tid, __amdgpu_buffer_
             const int i = C * DEN_CH + j, grp = i / S::GL, ii = i % S::GL, kb = ii / S::TG, t = ii % S::TG;
             if (ii == 0) acc.zero();
             if (j == 0 || t == 0) a4 = *reinterpret_cast<const uint4*>(x.fbase + x.foff + kb * XFRAG_STRIDE(MS));
-#ifndef DEN_DBG_NOFMA
             if constexpr (WT::HALF) acc.m[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, a4), __builtin_bit_cast(h16x8, ring.r[SLOT][j]), acc.m[t], 0, 0, 0);
             else acc.m[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a4), __builtin_bit_cast(bf16x8, ring.r[SLOT][j]), acc.m[t], 0, 0, 0);
-#else
-            acc.m[t].x += __uint_as_float(ring.r[SLOT][j].x ^ ring.r[SLOT][j].y ^ ring.r[SLOT][j].z ^ ring.r[SLOT][j].w ^ a4.x);
-#endif
             if (ii == S::GL - 1) {
                 // lanes 16s .. 16s+15: outputs (wave*TW + grp*TG + t)*16 + lane%16 of sample s = sum of the input parts
                 const int lane = tid & 63, sl = lane >> 4;
@@ -396,7 +384,7 @@ __device__ __forceinline__ void gemv_chunks(Ring& ring, int tid, __amdgpu_buffer
 // barrier B.  On entry and exit DEN_R chunks are in flight ahead of the consumer.
 template <typename WT, int V, int MS, int G, bool LAST>
 __device__ __forceinline__ void gemv_stream(Ring& ring, int tid, __amdgpu_buffer_rsrc_t rsrc, const MatOffs& mo, bool nskip,
-                                            const XIn& xin_, float* __restrict__ part, bool epi) {
+                                            const XIn& xin_, float* __restrict__ part) {
     typedef Prog<WT, V> P;
     constexpr int REL0 = (G == G_SKIP) ? -P::TS : P::start(P::pos(G));
     constexpr int NC = GS<WT, G>::TOT + (G == G_INP ? P::PAD : 0);   // in_proj also "consumes" the padding chunks
@@ -410,9 +398,6 @@ __device__ __forceinline__ void gemv_stream(Ring& ring, int tid, __amdgpu_buffer
     gemv_chunks<WT, V, MS, G, REL0, NC, BURST>(ring, tid, rsrc, mo, nskip, x, part, acc, std::make_integer_sequence<int, NC>{});
     __syncthreads();                                                  // barrier A: partial sums visible
     DEN_DBG(0);
-#ifdef DEN_SLEEP
-    if (!epi) __builtin_amdgcn_s_sleep(DEN_SLEEP);                    // let the epilogue wave's re-fills enter the fill queue first
-#endif
     refill<WT, V, G, REL0, NC - BURST>(ring, tid, rsrc, mo, nskip);
     if constexpr (BURST == 2) refill<WT, V, G, REL0, NC - 1>(ring, tid, rsrc, mo, nskip);
     acc.pin();
@@ -616,11 +601,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_sample(const DenKArgs ka) {
     const int seg = 64 / H;                      // lanes per attention head
     const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
     const int lane = tid0 & 63;
-#ifdef DEN_DBG_NOEPI   // timing probe: no epilogues (results are garbage)
-    const bool epi = false;
-#else
     const bool epi = wave < MS;                  // wave s turns sample s's partial sums into the next input vector
-#endif
     const int es = epi ? wave : 0;
     const int stg_sz = VP_LAYER + STG_TT + MS * N * 1024 + (CAQ ? 0 : MS * 256);
     const int ca_R = A.trow_per_sample ? 1 : A.steps;
@@ -727,7 +708,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_sample(const DenKArgs ka) {
             // ---- skip connection: Linear(cat[x, xs.pop()])  (cross_attention.py:77-79); input staged by the
             //      previous layer's last epilogue
             if (l >= 3) {
-                gemv_stream<WT, V, MS, G_SKIP, false>(ring, tid, wg, mo, nskip, xin, PART, epi);
+                gemv_stream<WT, V, MS, G_SKIP, false>(ring, tid, wg, mo, nskip, xin, PART);
                 if (epi) {
                     xr = f4_add(part256<WT, MS>(PART, es, lane), ld4(v_skip_b + 4 * lane));
                     put_x<WT, MS>(XB, es, 0, lane, xr);
@@ -736,7 +717,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_sample(const DenKArgs ka) {
             }
             // ---- sa_block: post-norm encoder layer over [x, xf.., emb]; only token 0 is kept
             //      (mdiff_transformer.py:292-297); K/V of xf and emb come from the tables.
-            gemv_stream<WT, V, MS, G_INP, false>(ring, tid, wg, mo, nskip, xin, PART, epi);
+            gemv_stream<WT, V, MS, G_INP, false>(ring, tid, wg, mo, nskip, xin, PART);
             if (epi) {
                 // in_proj output n in [0,768): q | k | v
                 const float4 q = f4_add(gemv_out<WT, MS, G_INP>(PART, es, 0, lane), ld4(v_in_b + 4 * lane));
@@ -785,7 +766,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_sample(const DenKArgs ka) {
             __syncthreads(); DEN_DBG(0);
             if constexpr (!FOLD) {
                 // ---- out_proj + residual + norm1
-                gemv_stream<WT, V, MS, G_OUTP, false>(ring, tid, wg, mo, nskip, xin, PART, epi);
+                gemv_stream<WT, V, MS, G_OUTP, false>(ring, tid, wg, mo, nskip, xin, PART);
                 if (epi) {
                     float4 o = f4_add(part256<WT, MS>(PART, es, lane), ld4(v_out_b + 4 * lane));
                     if (SAVE && dm) o = drop4(o, dm + DM_1 + 4 * lane);
@@ -798,7 +779,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_sample(const DenKArgs ka) {
                 __syncthreads(); DEN_DBG(0);
             }
             // ---- linear1 + relu  (N = 1024, one k-slice)
-            gemv_stream<WT, V, MS, G_L1, false>(ring, tid, wg, mo, nskip, xin, PART, epi);
+            gemv_stream<WT, V, MS, G_L1, false>(ring, tid, wg, mo, nskip, xin, PART);
             if (epi) {
 #pragma unroll
                 for (int j = 0; j < FF_SA / 256; ++j) {
@@ -811,7 +792,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_sample(const DenKArgs ka) {
             }
             __syncthreads(); DEN_DBG(0);
             // ---- linear2 + residual + norm2, then ca_block (mdiff_transformer.py:219-239, 152-163)
-            gemv_stream<WT, V, MS, G_L2, false>(ring, tid, wg, mo, nskip, xin, PART, epi);
+            gemv_stream<WT, V, MS, G_L2, false>(ring, tid, wg, mo, nskip, xin, PART);
             if (epi) {
                 float4 o2 = f4_add(part256<WT, MS>(PART, es, lane), ld4(v_l2b + 4 * lane));
                 if (SAVE && dm) o2 = drop4(o2, dm + DM_2 + 4 * lane);
@@ -834,7 +815,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_sample(const DenKArgs ka) {
             }
             __syncthreads(); DEN_DBG(0);
             if constexpr (CAQ) {
-                gemv_stream<WT, V, MS, G_CAQ, false>(ring, tid, wg, mo, nskip, xin, PART, epi);
+                gemv_stream<WT, V, MS, G_CAQ, false>(ring, tid, wg, mo, nskip, xin, PART);
                 if (epi) {
                     const float4 qv = f4_add(part256<WT, MS>(PART, es, lane), ld4(v_caq_b + 4 * lane));
                     const float mx = seg_reduce<true>(fmaxf(fmaxf(qv.x, qv.y), fmaxf(qv.z, qv.w)), seg);
@@ -877,7 +858,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_sample(const DenKArgs ka) {
                 }
                 __syncthreads(); DEN_DBG(0);
                 // ---- proj_out.out_layers + residual
-                gemv_stream<WT, V, MS, G_CAO, false>(ring, tid, wg, mo, nskip, xin, PART, epi);
+                gemv_stream<WT, V, MS, G_CAO, false>(ring, tid, wg, mo, nskip, xin, PART);
                 if (epi) {
                     xr = f4_add(xr, f4_add(part256<WT, MS>(PART, es, lane), ld4(v_cao_b + 4 * lane)));
                     if (SAVE && sv) st4(sv + DT_X3 + 4 * lane, xr);
@@ -886,7 +867,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_sample(const DenKArgs ka) {
                 __syncthreads(); DEN_DBG(0);
             }
             // ---- ffn.linear1 + gelu  (N = 128, four k-slices: lanes 0..31 hold 4 outputs each)
-            gemv_stream<WT, V, MS, G_F1, false>(ring, tid, wg, mo, nskip, xin, PART, epi);
+            gemv_stream<WT, V, MS, G_F1, false>(ring, tid, wg, mo, nskip, xin, PART);
             // request the next layer's operands (LDS-DMA into the other half of the double buffer) here, in the short
             // stages where the fill path has slack; the epilogue waves are busy and take no part
             if (!epi) stage_dma<MS, CAQ, MS, 1>(wave, lane, STG + (cur ^ 1) * stg_sz, vp, Ln, A.ttab + (size_t)(ln == 0 ? row_next : row) * SEEME_TROW, ln, A, b, N,
@@ -899,7 +880,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_sample(const DenKArgs ka) {
             }
             __syncthreads(); DEN_DBG(0);
             // ---- ffn.linear2 -> AdaLN
-            gemv_stream<WT, V, MS, G_F2, false>(ring, tid, wg, mo, nskip, xin, PART, epi);
+            gemv_stream<WT, V, MS, G_F2, false>(ring, tid, wg, mo, nskip, xin, PART);
             if (!epi) stage_dma<MS, CAQ, MS, 2>(wave, lane, STG + (cur ^ 1) * stg_sz, vp, Ln, A.ttab + (size_t)(ln == 0 ? row_next : row) * SEEME_TROW, ln, A, b, N,
                                                 A.trow_per_sample ? 0 : (ln == 0 ? step_next : step), ca_R);
             if (epi) {
@@ -912,7 +893,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_sample(const DenKArgs ka) {
             __syncthreads(); DEN_DBG(0);
             // ---- ffn.proj_out.out_layers + residual; its epilogue also prepares the input of the next layer
             //      (or, after the last layer, runs the stack norm and the scheduler step)
-            gemv_stream<WT, V, MS, G_FO, true>(ring, tid, wg, mo, nskip, xin, PART, epi);
+            gemv_stream<WT, V, MS, G_FO, true>(ring, tid, wg, mo, nskip, xin, PART);
             if (l + 1 < SEEME_DEN_NL) {
                 if (epi) {
                     xr = f4_add(xr, f4_add(part256<WT, MS>(PART, es, lane), ld4(v_fo_b + 4 * lane)));

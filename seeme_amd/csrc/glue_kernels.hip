@@ -107,9 +107,6 @@ __global__ __launch_bounds__(256) void k_glue_mid(SeemeGlueMid a) {
 
 // ------------------------------------------------------------------ grouped GEMM
 #define GG_T 64
-#ifndef GG_MFMA
-#define GG_MFMA 1
-#endif
 #ifndef GG_K
 #define GG_K 64          // k-step: 16 loads of A and 16 of B in flight per thread -- the weights are cold in HBM every step
 #endif                   // (PointNet streams GBs in between), so the tile time is round trips, not FLOPs
@@ -238,7 +235,6 @@ __global__ __launch_bounds__(256) void k_gg(const SeemeGemmProblem* __restrict__
             Bs[kb][b_j(e)] = okb ? rb[e] : 0.f;
         }
     };
-#if GG_MFMA
     // inner product on the matrix cores: v_mfma_f32_32x32x2_f32 is an fp32 FMA chain (same arithmetic as the vector-ALU loop it
     // replaces) that costs one issue slot per 4096 FLOPs instead of one per 256 -- the vector ALU is left to the staging code.
     // Wave (wi, wj) owns the 32 x 32 quadrant; a lane supplies A[i = lane % 32][k + lane / 32] and B[k + lane / 32][j = lane % 32].
@@ -318,64 +314,6 @@ __global__ __launch_bounds__(256) void k_gg(const SeemeGemmProblem* __restrict__
             for (int v = 0; v < 16; ++v) if (row(v) < M && j < N) cb[row(v) * P.ldc + j] = val[v];
         }
     }
-#else
-    float acc[4][4] = {};
-    const int ty = t >> 4, tx = t & 15;
-    fetch();
-    while (seg < nseg) {
-        stage(k0, P.seg_len[seg]);
-        __syncthreads();
-        k0 += GG_K;
-        if (k0 >= P.seg_len[seg]) { k0 = 0; ++seg; }
-        if (seg < nseg) fetch();
-        // fragments of 4 k at a time, the next 4 in flight while these are multiplied: with one wave per SIMD nothing else
-        // hides the LDS latency (a read-wait-multiply loop ran at ~230 cycles per k)
-        float4 fa[2][4], fb[2][4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            fa[0][q] = *reinterpret_cast<const float4*>(&As[q][ty * 4]);
-            fb[0][q] = *reinterpret_cast<const float4*>(&Bs[q][tx * 4]);
-        }
-#pragma unroll
-        for (int c = 0; c < GG_K / 4; ++c) {
-            if (c + 1 < GG_K / 4) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    fa[(c + 1) & 1][q] = *reinterpret_cast<const float4*>(&As[4 * (c + 1) + q][ty * 4]);
-                    fb[(c + 1) & 1][q] = *reinterpret_cast<const float4*>(&Bs[4 * (c + 1) + q][tx * 4]);
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 av = fa[c & 1][q], bv = fb[c & 1][q];
-                const float aa[4] = {av.x, av.y, av.z, av.w}, bb[4] = {bv.x, bv.y, bv.z, bv.w};
-#pragma unroll
-                for (int x = 0; x < 4; ++x)
-#pragma unroll
-                    for (int y = 0; y < 4; ++y) acc[x][y] = fmaf(aa[x], bb[y], acc[x][y]);
-            }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int x = 0; x < 4; ++x) {
-        const int i = i0 + ty * 4 + x;
-        if (i >= M) continue;
-#pragma unroll
-        for (int y = 0; y < 4; ++y) {
-            const int j = j0 + tx * 4 + y;
-            if (j >= N) continue;
-            float v = acc[x][y];
-            if (P.bias) v += P.bias[j];
-            if (P.epi == 1) v *= dsilu_f(P.e0[(long)i * P.e_ld + j]);
-            else if (P.epi == 2) v *= P.alpha;
-            if (P.addend) v += P.addend[(long)i * P.add_ld + j];
-            float* dst = P.c + c_boff + (long)i * P.ldc + j;
-            if (P.accumulate == 2) atomicAdd(dst, v);          // split reductions (nbatch members sharing one C)
-            else *dst = P.accumulate ? *dst + v : v;
-        }
-    }
-#endif
     if (want_cs) {                      // thread (t & 15, t >> 4) holds the partial sums of i = 4 (t & 15) + c over its k's
 #pragma unroll
         for (int c = 0; c < 4; ++c) cs[t >> 4][4 * (t & 15) + c] = csum[c];
@@ -431,9 +369,6 @@ typedef float g1_f32x4 __attribute__((ext_vector_type(4)));
 typedef g1_f32x4 __attribute__((address_space(1))) g1_gfloat4;
 typedef float g1_f32x16 __attribute__((ext_vector_type(16)));
 
-#ifndef G1_PIN
-#define G1_PIN 1
-#endif
 template <bool NT>
 __global__ __launch_bounds__(256, 2) void k_gemm128(const float* __restrict__ A, long lda, const float* __restrict__ B, long ldb,
                                                     float* __restrict__ C, long ldc, int K, const float* __restrict__ bias,
@@ -502,7 +437,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm128(const float* __restrict__ A,
                 for (int x = 0; x < 2; ++x)
 #pragma unroll
                     for (int y = 0; y < 2; ++y) acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c & 1][q][x], fb[c & 1][q][y], acc[x][y], 0, 0, 0);
-#if G1_PIN
             // pin the interleave: one fragment read of the NEXT chunk behind each MFMA of this one (left alone the scheduler reads a
             // k-pair's fragments, waits lgkmcnt(0), multiplies, and the LDS latency is exposed 16 times per k-step)
 #pragma unroll
@@ -510,7 +444,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm128(const float* __restrict__ A,
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             }
-#endif
         }
         if (s + 1 < nk) stage(buf ^ 1);
         __syncthreads();

@@ -92,10 +92,8 @@ __device__ __forceinline__ void tile_gemm_h16(const unsigned short* __restrict__
         for (int u = 0; u < PF; ++u) {
             const int kb = kb0 + u;                          // < K32 - 1 here
             const int ka = kb + H16_ALA < K32 ? kb + H16_ALA : K32 - 1;
-#ifndef H16_DBG_NOAREAD        // timing-only ablation: the A fragments of the first k-blocks are reused (wrong results)
 #pragma unroll
             for (int mt = 0; mt < MTL; ++mt) ab[(u + H16_ALA) % AS][mt] = *reinterpret_cast<const uint4*>(ap + mt * 16 * lda + ka * 32);
-#endif
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int mt = 0; mt < MTL; ++mt)
@@ -103,11 +101,9 @@ __device__ __forceinline__ void tile_gemm_h16(const unsigned short* __restrict__
                 for (int nt = 0; nt < NTL; ++nt)
                     acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, ab[u % AS][mt]), __builtin_bit_cast(h16x8, br[u][nt]), acc[mt][nt], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-#ifndef H16_DBG_NOREFILL       // timing-only ablation: the MFMAs keep reading the primed k-blocks (wrong results)
             const int kn = kb + PF < K32 ? kb + PF : K32 - 1;
 #pragma unroll
             for (int nt = 0; nt < NTL; ++nt) br[u][nt] = loadb(nt, kn);
-#endif
         }
     }
 #pragma unroll
@@ -129,22 +125,15 @@ __device__ __forceinline__ void tile_gemm_h16(const unsigned short* __restrict__
 }
 // B fragments from fragment-packed weights: Wp[(ntile*kstride + kb)*64 + lane]; n-tiles clamped to ntiles-1.  Buffer loads:
 // one descriptor per matrix, the lane's 16-byte offset in a VGPR, (n-tile, k-block) as a SCALAR byte offset -- no 64-bit
-// per-lane address arithmetic and half the address traffic of global_load (PACKED_GLOBAL_LOADS=1 keeps the old form).
-#ifndef PACKED_GLOBAL_LOADS
-#define PACKED_GLOBAL_LOADS 0
-#endif
+// per-lane address arithmetic and half the address traffic of the global_load form this replaced.
 struct PackedSrc {
-    __amdgpu_buffer_rsrc_t rs; const uint4* wp; int kstride, ntile0, ntiles; unsigned voff;
+    __amdgpu_buffer_rsrc_t rs; int kstride, ntile0, ntiles; unsigned voff;
     __device__ __forceinline__ PackedSrc(const uint4* __restrict__ Wp, int kstride_, int ntile0_, int ntiles_)
-        : rs(__builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(Wp), 0, 0x7FFFFFF0, 0x00020000)), wp(Wp), kstride(kstride_),
+        : rs(__builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(Wp), 0, 0x7FFFFFF0, 0x00020000)), kstride(kstride_),
           ntile0(__builtin_amdgcn_readfirstlane(ntile0_)), ntiles(ntiles_), voff((threadIdx.x & 63) * 16u) {}
     __device__ __forceinline__ uint4 operator()(int nt, int kb) const {
         int t = ntile0 + nt; t = t < ntiles ? t : ntiles - 1;
-#if PACKED_GLOBAL_LOADS
-        return wp[((size_t)t * kstride + kb) * 64 + (threadIdx.x & 63)];
-#else
         return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, (unsigned)(t * kstride + kb) * 1024u, 0));
-#endif
     }
 };
 template <int MTL, int NTL, int PF = H16_PF>
@@ -831,9 +820,6 @@ __device__ __forceinline__ void rows_to_h16(unsigned short* Xh, int ldh, int row
 // (row-major K rows / V^T rows made every wave-load touch 16 rows x 64 B; the V^T rows were written two bytes at a time).
 // Value granules of keys in [S, spv) are written as zeros by the tiles that cover them (P = 0 there, but 0 x garbage is not);
 // key rows in [S, 16 NT16) stay unwritten: their score columns are masked by a select.
-#ifndef LAYER_TAIL_STORES_LAST
-#define LAYER_TAIL_STORES_LAST 1
-#endif
 template <int WAVES, int RW>
 __device__ __forceinline__ void tail_store_q(const unsigned short* Oh, int ld, unsigned short* __restrict__ q_out, size_t base, int q0, int S) {
     constexpr int NT = 64 * WAVES;
@@ -889,21 +875,6 @@ __device__ __forceinline__ void tail_qkv_rows(const unsigned short* Xh, unsigned
     // queued behind the previous part's stores waited for their write acknowledgements (round 2 measured 14-22 k cycles for this tail against
     // 2.7 k for the out_proj of the same shape).  q and K wait in the two halves of the output region (the second without row padding: together
     // they are exactly the fp32 tile's 32 x 264 x 4 bytes), V in its accumulators.
-#if !LAYER_TAIL_STORES_LAST
-    for (int y = 0; y < 3; ++y) {
-        f32x4 acc[MTL][NTL];
-        acc_zero(acc);
-        const BiasRegs<NTL> bias = bias_load<NTL>(qkv_b, y * 256 + wave * CW, 768);
-        gemm_packed<MTL, NTL, PF>(Xh, ldq, qkv_w, 8, y * 16 + wave * NTL, 48, 8, acc, ring_t);
-        if (y < 2) prime_packed(ring_t, qkv_w, 8, (y + 1) * 16 + wave * NTL, 48, 8);
-        __syncthreads();                    // the previous part's stores have read the output tile
-        acc_store_h16<MTL, NTL>(acc, Oh, ldq, wave * CW, bias, SEEME_ACT_NONE);
-        __syncthreads();
-        if (y == 0) tail_store_q<WAVES, RW>(Oh, ldq, q_out, base, q0, S);
-        else if (y == 1) tail_store_k<WAVES, RW>(Oh, ldq, kp_out, b, q0, S, NT16);
-        else tail_store_v<WAVES, RW>(Oh, ldq, vp_out, b, q0, S, KB);
-    }
-#else
     constexpr int ldk = 256;                                   // K's staging rows: unpadded (see above)
     unsigned short* const OhK = Oh + ROWS * ldq;
     {
@@ -936,7 +907,6 @@ __device__ __forceinline__ void tail_qkv_rows(const unsigned short* Xh, unsigned
         __syncthreads();
         tail_store_v<WAVES, RW>(Oh, ldq, vp_out, b, q0, S, KB);
     }
-#endif
 }
 
 // debug stamps of a layer that has the next layer's QKV as its tail (the last launch of those in a pass is what is read back)
