@@ -545,6 +545,18 @@ size_t seeme_hyp_metrics_workspace_bytes(int B, int K, int T);
 int seeme_hyp_metrics(const float* jts_pred, const float* jts_ref, const int32_t* lengths, int B, int K, int T,
                       float* per_hyp, float* per_seq, void* ws, size_t ws_bytes, void* stream);
 
+/* Pairwise distances of the K hypotheses of a sequence and their medoid (the label-free choice among the K draws).
+ * jts_pred [B,K,T,24,3] as above, 16-byte aligned; lengths [B], nvalid = clamp(len, 0, T).  With a_k the prediction of hypothesis k
+ * after the alignment of seeme_hyp_metrics (minus its own first-frame joint 15, then minus each frame's own joint 0):
+ * dist[b,i,j] = 1000 x the mean over the nvalid frames and the 24 joints of |a_i - a_j| (mm).  The diagonal is exactly 0 and the
+ * matrix exactly symmetric (every unordered pair is computed once and mirrored); sum_{i,j} dist[b] / (K (K-1)) / 2 is APD_JOINTS[b].
+ * medoid[b] = argmin over i of sum_j dist[b,i,j], the sum taken in j order in fp32; the LOWEST index wins a tie (so K = 2 gives 0).
+ * nvalid = 0 gives a zero matrix and medoid 0; K = 1 gives [[0]] and medoid 0.  K <= 32.  Frames past nvalid are never read.  No
+ * atomics: bitwise reproducible.  The workspace (16-byte aligned) holds the per-chunk partial sums of the pairs. */
+size_t seeme_hyp_pairdist_workspace_bytes(int B, int K, int T);   /* 0 for bad sizes */
+int seeme_hyp_pairdist(const float* jts_pred, const int32_t* lengths, int B, int K, int T, float* dist, int32_t* medoid,
+                       void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ per-frame mesh metrics (csrc/mesh_metrics.hip)
  * Frame-level primitives of the EgoHMR tables (test_egohmr.py:463-492, 540-549): one float per frame, fp32 metres in and out, a
  * frame whose map entry is negative is skipped and gets 0; the caller averages over the valid frames of a sequence and chunks the

@@ -210,6 +210,8 @@ _SIGNATURES = {
     "seeme_smpl_lbs": (C.c_int, [C.POINTER(SmplModel), fp, fp, C.c_int, fp, C.c_int, fp, fp, fp, C.c_size_t, fp]),
     "seeme_hyp_metrics_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "seeme_hyp_metrics": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, C.c_int, fp, fp, fp, C.c_size_t, fp]),
+    "seeme_hyp_pairdist_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "seeme_hyp_pairdist": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, fp, fp, fp, C.c_size_t, fp]),
     "seeme_pa_mpjpe_frames": (C.c_int, [fp, fp, fp, C.c_int, fp, fp]),
     "seeme_mesh_v2v_frames": (C.c_int, [fp, fp, fp, fp, fp, C.c_int, C.c_int, fp, fp]),
     "seeme_scene_min_dist2_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -54,6 +54,8 @@ def build_parser(phase: str) -> argparse.ArgumentParser:
     s.add_argument("--folder", type=str, default=None, help="override FOLDER (experiment root)")
     s.add_argument("--checkpoint", type=str, default=None, help="override TEST.CHECKPOINTS")
     s.add_argument("--num_hypotheses", type=int, default=None, help="override TEST.NUM_HYPOTHESES (draws per sequence, 1..32)")
+    s.add_argument("--hyp_select", type=str, default=None, choices=["first", "medoid"],
+                   help="override TEST.HYP_SELECT: the draw that stands for its sequence when --num_hypotheses > 1 (medoid: label-free)")
     s.add_argument("--mesh_metrics", action="store_true",
                    help="set TEST.MESH_METRICS: PA-MPJPE, V2V and body-scene contact per hypothesis (seeme_amd/mesh_metrics.py)")
     return p
@@ -67,6 +69,8 @@ def load_cfg(args, phase: str):
             cfg.NAME = "debug--" + str(cfg.get("NAME", "exp"))       # mld/config.py:190-193
     if getattr(args, "num_hypotheses", None) is not None:
         cfg.TEST.NUM_HYPOTHESES = args.num_hypotheses
+    if getattr(args, "hyp_select", None) is not None:
+        cfg.TEST.HYP_SELECT = args.hyp_select
     if getattr(args, "mesh_metrics", False):
         cfg.TEST.MESH_METRICS = True
     if args.folder:
@@ -267,6 +271,7 @@ def test_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=None
         model.EgoMetric.reset()
         model.HypMetric.reset()
         model.MeshMetric.reset()
+        model.SelMetric.reset()
         t0 = time.perf_counter()
         with torch.no_grad():
             if hasattr(dm, "iterate"):  # files: ONE pass over the test split, every sequence exactly once over the ranks (test.py:115-133)
@@ -288,6 +293,8 @@ def test_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=None
             metrics["samples_per_s"] = model.num_hypotheses * metrics["seqs_per_s"]
         if model.mesh_metrics:          # PA-MPJPE / V2V (best and mean over the kept hypotheses) and, with a scene, distance and contact
             metrics.update(model.MeshMetric.compute(D.reduce_sums(model.MeshMetric.sums().to(dev)).cpu()))
+        if model.hyp_select == "medoid" and model.num_hypotheses > 1:    # the errors of the label-free choice among the K draws
+            metrics.update(model.SelMetric.compute(D.reduce_sums(model.SelMetric.sums().to(dev)).cpu()))
         log.info("Replication %d: %s", rep, json.dumps({k: round(v, 4) for k, v in metrics.items()}))
         for k, v in metrics.items():
             all_metrics.setdefault(k, []).append(float(v))

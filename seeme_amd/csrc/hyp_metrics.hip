@@ -247,3 +247,181 @@ extern "C" int seeme_hyp_metrics(const float* jts_pred, const float* jts_ref, co
     hipLaunchKernelGGL(k_hyp_final, dim3(B), dim3(128), 0, st, (const float*)ws, lengths, B, K, NC, per_hyp, per_seq);
     return seeme_check_launch("k_hyp_final");
 }
+
+// ------------------------------------------------------------------ pairwise distances of the K hypotheses and their medoid
+// dist[b,i,j] = 1000 x the mean over the nvalid = clamp(len, 0, T) frames and the 24 joints of |a_i - a_j|, a_k the prediction of
+// hypothesis k aligned as above; medoid[b] = argmin_i sum_j dist[b,i,j] (fp32, j order, lowest index on a tie).
+//
+// Partition: one workgroup (256 lanes) per (sequence b, chunk of FC frames, the rule of hyp_chunk_frames).  The K aligned rows of a
+// frame live in LDS as [K][72] (stride 73: odd, so the K <= 32 rows a wave touches at one coordinate sit on distinct banks); two
+// slots, the next frame's float4 loads in flight while the current one is reduced.  There is no second difference, so no halo frame
+// and no ring.  A lane owns whole pairs (i < j, row-major; K = 32 has 496, so lanes 0..239 own two) and loops over the 24 joints;
+// it sums its pairs over the chunk's frames in registers and writes them to the workspace [B][chunks][pairs] -- no cross-lane
+// reduction.  k_hyp_pair_final adds the chunks in chunk order, normalises, mirrors the matrix and takes the argmin.  No atomics.
+#define HYP_PAIRS_MAX (HYP_KMAX * (HYP_KMAX - 1) / 2)                        // 496
+#define HYP_NPL ((HYP_PAIRS_MAX + HYP_THREADS - 1) / HYP_THREADS)            // pairs per lane (2)
+#define HYP_PROW (HYP_ROW + 1)
+#define HYP_PLD ((HYP_KMAX * HYP_Q + HYP_THREADS - 1) / HYP_THREADS)         // float4 loads of one frame per lane (3)
+
+__global__ __launch_bounds__(HYP_THREADS) void k_hyp_pair_partial(const float* __restrict__ pred, const int32_t* __restrict__ lengths,
+                                                                  int K, int T, int FC, float* __restrict__ slab) {
+    __shared__ float rows[2][HYP_KMAX][HYP_PROW];        // aligned joints of the K hypotheses
+    __shared__ float hd[HYP_KMAX][3];                    // first frame's joint 15
+
+    const int tid = threadIdx.x, b = blockIdx.y, chunk = blockIdx.x, NC = gridDim.x;
+    const int len = lengths[b];
+    const int nvalid = len < 0 ? 0 : (len > T ? T : len);
+    const int t0 = chunk * FC, t1 = min(t0 + FC, nvalid);
+    const int P = K * (K - 1) / 2;
+    float* out = slab + ((size_t)b * NC + chunk) * P;
+    if (t0 >= nvalid) {                                  // nothing valid here: the workspace is not zeroed by anyone else
+        for (int i = tid; i < P; i += HYP_THREADS) out[i] = 0.f;
+        return;
+    }
+    const float* predb = pred + (size_t)b * K * T * HYP_ROW;
+    const int nld = K * HYP_Q;
+
+    if (tid < K) {
+        const float* r0 = predb + (size_t)tid * T * HYP_ROW + 15 * 3;
+        hd[tid][0] = r0[0]; hd[tid][1] = r0[1]; hd[tid][2] = r0[2];
+    }
+    // this lane's pairs: p = tid + r * 256 -> (i, j), i < j, row-major over the upper triangle
+    int pi[HYP_NPL], pj[HYP_NPL];
+#pragma unroll
+    for (int r = 0; r < HYP_NPL; ++r) {
+        int rem = tid + r * HYP_THREADS, i = 0;
+        if (rem < P) {
+            while (rem >= K - 1 - i) { rem -= K - 1 - i; ++i; }
+            pi[r] = i; pj[r] = i + 1 + rem;
+        } else {
+            pi[r] = pj[r] = -1;
+        }
+    }
+
+    float4 v[HYP_PLD], p0[HYP_PLD];
+    auto issue = [&](int f) {
+#pragma unroll
+        for (int r = 0; r < HYP_PLD; ++r) {
+            const int e = tid + r * HYP_THREADS;
+            if (e < nld) {
+                const int row = e / HYP_Q, q = e - row * HYP_Q;
+                const float4* src = (const float4*)(predb + ((size_t)row * T + f) * HYP_ROW);
+                v[r] = src[q];
+                p0[r] = src[0];
+            }
+        }
+    };
+    auto commit = [&](int slot) {
+#pragma unroll
+        for (int r = 0; r < HYP_PLD; ++r) {
+            const int e = tid + r * HYP_THREADS;
+            if (e < nld) {
+                const int row = e / HYP_Q, q = e - row * HYP_Q;
+                const float h0 = hd[row][0], h1 = hd[row][1], h2 = hd[row][2];
+                const float g0 = p0[r].x - h0, g1 = p0[r].y - h1, g2 = p0[r].z - h2;      // pelvis - head(frame 0)
+                const float vv[4] = {v[r].x, v[r].y, v[r].z, v[r].w};
+                int c = (q * 4) % 3;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float h = c == 0 ? h0 : (c == 1 ? h1 : h2);
+                    const float g = c == 0 ? g0 : (c == 1 ? g1 : g2);
+                    rows[slot][row][q * 4 + i] = (vv[i] - h) - g;
+                    c = c == 2 ? 0 : c + 1;
+                }
+            }
+        }
+    };
+
+    float acc[HYP_NPL];
+#pragma unroll
+    for (int r = 0; r < HYP_NPL; ++r) acc[r] = 0.f;
+
+    issue(t0);
+    __syncthreads();                                              // hd
+    for (int f = t0; f < t1; ++f) {
+        const int s = (f - t0) & 1;
+        commit(s);
+        __syncthreads();                                          // slot s complete; every lane is done with slot s^1 (frame f-1)
+        if (f + 1 < t1) issue(f + 1);
+#pragma unroll
+        for (int r = 0; r < HYP_NPL; ++r) {
+            if (pi[r] >= 0) {
+                const float* a = rows[s][pi[r]];
+                const float* c = rows[s][pj[r]];
+                float x = 0.f;
+#pragma unroll 8
+                for (int j3 = 0; j3 < HYP_ROW; j3 += 3) {
+                    const float ex = a[j3] - c[j3], ey = a[j3 + 1] - c[j3 + 1], ez = a[j3 + 2] - c[j3 + 2];
+                    x += sqrtf(ex * ex + ey * ey + ez * ez);
+                }
+                acc[r] += x;
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < HYP_NPL; ++r) {
+        const int p = tid + r * HYP_THREADS;
+        if (p < P) out[p] = acc[r];
+    }
+}
+
+// one workgroup per sequence, one lane per pair: the chunks in chunk order, x1000 / 24 / nvalid, both halves of the matrix and a zero
+// diagonal; then the row sums in j order and the lowest index of the smallest one
+__global__ __launch_bounds__(512) void k_hyp_pair_final(const float* __restrict__ slab, const int32_t* __restrict__ lengths, int K, int T,
+                                                        int NC, float* __restrict__ dist, int32_t* __restrict__ medoid) {
+    __shared__ float D[HYP_KMAX][HYP_KMAX + 1];
+    __shared__ float rs[HYP_KMAX];
+    const int b = blockIdx.x, p = threadIdx.x, P = K * (K - 1) / 2;
+    const int len = lengths[b];
+    const int nvalid = len < 0 ? 0 : (len > T ? T : len);
+    float* db = dist + (size_t)b * K * K;
+    if (p < P) {
+        const float* s = slab + (size_t)b * NC * P + p;
+        float x = 0.f;
+#pragma unroll 4
+        for (int c = 0; c < NC; ++c) x += s[(size_t)c * P];
+        const float d = nvalid > 0 ? x / (float)HYP_NJ / (float)nvalid * 1000.f : 0.f;
+        int rem = p, i = 0;
+        while (rem >= K - 1 - i) { rem -= K - 1 - i; ++i; }
+        const int j = i + 1 + rem;
+        D[i][j] = d; D[j][i] = d;
+        db[i * K + j] = d; db[j * K + i] = d;
+    }
+    if (p < K) { D[p][p] = 0.f; db[p * K + p] = 0.f; }
+    __syncthreads();
+    if (p < K) {
+        float x = 0.f;
+        for (int j = 0; j < K; ++j) x += D[p][j];
+        rs[p] = x;
+    }
+    __syncthreads();
+    if (p == 0) {
+        int best = 0;
+        for (int i = 1; i < K; ++i) if (rs[i] < rs[best]) best = i;
+        medoid[b] = best;
+    }
+}
+
+extern "C" size_t seeme_hyp_pairdist_workspace_bytes(int B, int K, int T) {
+    if (B < 1 || K < 1 || K > HYP_KMAX || T < 1) return 0;
+    const int FC = hyp_chunk_frames(B, T), P = K * (K - 1) / 2;
+    return (size_t)B * ((T + FC - 1) / FC) * (P > 0 ? P : 1) * sizeof(float);       // K = 1 has no pair: one unused float per chunk
+}
+
+extern "C" int seeme_hyp_pairdist(const float* jts_pred, const int32_t* lengths, int B, int K, int T, float* dist, int32_t* medoid,
+                                  void* ws, size_t ws_bytes, void* stream) {
+    if (B < 1 || B > 65535) return seeme_fail("hyp_pairdist: B must be in 1..65535");
+    if (K < 1 || K > HYP_KMAX) return seeme_fail("hyp_pairdist: K must be in 1..32");
+    if (T < 1) return seeme_fail("hyp_pairdist: T must be >= 1");
+    if (!jts_pred || !lengths || !dist || !medoid || !ws) return seeme_fail("hyp_pairdist: null pointer");
+    if (((uintptr_t)jts_pred | (uintptr_t)ws) & 15) return seeme_fail("hyp_pairdist: joints and workspace must be 16-byte aligned");
+    if (ws_bytes < seeme_hyp_pairdist_workspace_bytes(B, K, T)) return seeme_fail("hyp_pairdist: workspace too small");
+    const int FC = hyp_chunk_frames(B, T), NC = (T + FC - 1) / FC;
+    hipStream_t st = (hipStream_t)stream;
+    if (K > 1) {                                                                  // K = 1: no pair, nothing to sum
+        hipLaunchKernelGGL(k_hyp_pair_partial, dim3(NC, B), dim3(HYP_THREADS), 0, st, jts_pred, lengths, K, T, FC, (float*)ws);
+        if (int rc = seeme_check_launch("k_hyp_pair_partial")) return rc;
+    }
+    hipLaunchKernelGGL(k_hyp_pair_final, dim3(B), dim3(512), 0, st, (const float*)ws, lengths, K, T, NC, dist, medoid);
+    return seeme_check_launch("k_hyp_pair_final");
+}

@@ -39,7 +39,8 @@ import torch.nn as nn
 from . import geometry as G
 from .config import instantiate_from_config
 from .denoiser_autograd import denoiser_forward_torch
-from .hyp_metrics import K_MAX, HypothesisMetrics, best_index, hyp_metrics_hip, keep_mask
+from .hyp_metrics import (K_MAX, HypothesisMetrics, SelectionMetrics, best_index, check_select, hyp_metrics_hip, hyp_pairdist_hip,
+                          keep_mask, select_index)
 from .mesh_metrics import MeshMetrics, mesh_metrics_eval
 from .resnet import ResNet50
 from .respointnet import ResnetPointnet
@@ -362,6 +363,9 @@ class MLD(nn.Module):
             raise ValueError("TEST.CFG_SCENE_ORDER must be 'reference' or 'fixed'")
         # hypotheses per sequence in ONE evaluation pass (condition encoded once, errors and diversity per sequence): 1 = today's path
         self.num_hypotheses = self._check_num_hypotheses(cfg.TEST.get("NUM_HYPOTHESES", 1), "TEST.NUM_HYPOTHESES")
+        # which of the K > 1 hypotheses stands for its sequence in the keys of a K = 1 result: 'first' (hypothesis 0, today's result) or
+        # 'medoid' (smallest total distance to the other draws: seeme_hyp_pairdist; needs no ground truth)
+        self.hyp_select = check_select(cfg.TEST.get("HYP_SELECT", "first"), "TEST.HYP_SELECT")
         # PA-MPJPE, V2V and body-scene contact per hypothesis (seeme_amd/mesh_metrics.py): off = today's result, key for key
         self.mesh_metrics = cfg.TEST.get("MESH_METRICS", False)
         if not isinstance(self.mesh_metrics, bool):
@@ -424,6 +428,7 @@ class MLD(nn.Module):
         self.EgoMetric = EgoMetrics()
         self.HypMetric = HypothesisMetrics()
         self.MeshMetric = MeshMetrics()
+        self.SelMetric = SelectionMetrics()
         self.do_classifier_free_guidance = self.guidance_scale > 1.0
         self.renorm = datamodule.renorm if datamodule is not None else (lambda x: x)
         self.times: List[float] = []
@@ -770,17 +775,20 @@ class MLD(nn.Module):
 
     # ------------------------------------------------------------------ evaluation (mld.py:1076-1905, live part)
     @torch.no_grad()
-    def ego_eval(self, batch, latents=None, want_vertices=False, cond_noise=None, step_noise=None, num_hypotheses=None):
+    def ego_eval(self, batch, latents=None, want_vertices=False, cond_noise=None, step_noise=None, num_hypotheses=None,
+                 hyp_select=None):
         """Injection points for parity tests (not in the reference): latents [B,1,256] initial noise; cond_noise = eps
         [1,B,256] of the condition sample (stage 'vae': of the target's sample), or a pair (eps_cond, eps_uncond) with
         classifier-free guidance; step_noise for DDPM.
 
         num_hypotheses K (None: TEST.NUM_HYPOTHESES) > 1 draws K hypotheses per sequence from ONE encode of the condition
         (``_ego_eval_hypotheses``): the injection points then have B*K rows, row b*K + k = hypothesis k of sequence b.  K = 1 is the
-        path below, unchanged."""
+        path below, unchanged.  hyp_select (None: TEST.HYP_SELECT) 'first' | 'medoid' chooses the hypothesis that fills the keys of a
+        K = 1 result; it applies only for K > 1."""
         K = self.num_hypotheses if num_hypotheses is None else self._check_num_hypotheses(num_hypotheses, "num_hypotheses")
+        select = self.hyp_select if hyp_select is None else check_select(hyp_select, "hyp_select")
         if K > 1:
-            return self._ego_eval_hypotheses(batch, K, latents, want_vertices, cond_noise, step_noise)
+            return self._ego_eval_hypotheses(batch, K, latents, want_vertices, cond_noise, step_noise, select)
         int_gt = None
         if self.pose_estimation_task:       # batch ends with the interactee's ground truth (mld.py:1119-1131)
             batch, int_gt = tuple(batch[:-3]), tuple(t.float() for t in batch[-3:])
@@ -911,11 +919,12 @@ class MLD(nn.Module):
                                                  step_noise=None if step_noise is None else step_noise[:, lo:hi]))
         return out[0] if len(out) == 1 else torch.cat(out, dim=1)            # [1,rows,256]
 
-    def _ego_eval_hypotheses(self, batch, K, latents=None, want_vertices=False, cond_noise=None, step_noise=None):
+    def _ego_eval_hypotheses(self, batch, K, latents=None, want_vertices=False, cond_noise=None, step_noise=None, select="first"):
         """ego_eval for K > 1.  Once per SEQUENCE: the PointNet scene code and its token (and the zero-scene token under guidance),
         the image token, vae.encode_dist of the interactee (and of the zero motion), the reference and interactee joints.  Per
         HYPOTHESIS: the posterior draw of the condition token, the initial latent, the DDPM step noise, decode, renorm, SMPL joints.
-        Rows are sequence-major (b*K + k).  The keys of the K = 1 result are filled from hypothesis 0."""
+        Rows are sequence-major (b*K + k).  The keys of the K = 1 result are filled from hypothesis 0, or with select 'medoid' from
+        the medoid of the K draws of each sequence (hm gains PAIR_DIST, medoid_index and selected_index)."""
         int_gt = None
         if self.pose_estimation_task:
             batch, int_gt = tuple(batch[:-3]), tuple(t.float() for t in batch[-3:])
@@ -994,7 +1003,6 @@ class MLD(nn.Module):
         del decoded
         out_ref = self._feats_to_joints(f_ref, b_ref, want_vertices)
         joints_ref = out_ref[0] if want_vertices else out_ref
-        f_rst0 = f_rst.view(B, K, min_len, -1)[:, 0].contiguous()
         joints_all = joints_all.view(B, K, min_len, 24, 3)
         f_int_r = self.renorm(self._wearer_features(feats_ref[:, :min_len], transl[:, :, :min_len], 1))
         joints_int = self._feats_to_joints(f_int_r, beta[:, 1, :min_len])
@@ -1023,16 +1031,24 @@ class MLD(nn.Module):
         hm["have_quat"] = q_all is not None
         # (the 'test' inclusion rule; allsplit_step, which knows the split, puts the 'val' rule's index there on 'val')
         hm["best_index"] = best_index(hm["MPJPE"], keep_mask(hm, "test", hm["have_quat"]))
-        rs = {"m_ref": f_ref, "m_rst": f_rst0, "joints_ref": joints_ref, "joints_rst": joints_all[:, 0].contiguous(),
-              "orientation_quat_rst": None if q_all is None else q_all.reshape(B, K, min_len, 4)[:, 0].reshape(-1, 4).contiguous(),
+        if select == "medoid":              # label-free choice: one seeme_hyp_pairdist pass over the same joints
+            hm.update(hyp_pairdist_hip(joints_all, lengths))
+            hm["selected_index"] = select_index(hm, select)
+            rows = torch.arange(B, device=dev)
+            pick = lambda t: t[rows, hm["selected_index"]].contiguous()              # [B,K,...] -> [B,...]
+        else:
+            pick = lambda t: t[:, 0].contiguous()
+        f_rst0 = pick(f_rst.view(B, K, min_len, -1))
+        rs = {"m_ref": f_ref, "m_rst": f_rst0, "joints_ref": joints_ref, "joints_rst": pick(joints_all),
+              "orientation_quat_rst": None if q_all is None else pick(q_all.reshape(B, K, min_len, 4)).reshape(-1, 4),
               "orientation_quat_ref": q_ref,
               "root_interactee": joints_int[:, :, 0], "joints_interactee": joints_int,
               "orientation_quat_int": quat(f_int_r), "joints_interactee_gt": joints_int_gt, "lengths": lengths,
-              "list_names": {}, "lat_t": z.view(1, B, K, -1)[:, :, 0].contiguous(),
+              "list_names": {}, "lat_t": pick(z.view(B, K, -1))[None],
               "joints_rst_all": joints_all, "m_rst_all": f_rst.view(B, K, min_len, -1), "lat_t_all": z, "hyp_metrics": hm}
         if self.mesh_metrics:
             rs["mesh_metrics"] = self._mesh_metrics(f_rst, f_ref, b_ref, o_ref, lengths, K, scene)
-        if want_vertices:                                                   # meshes of hypothesis 0 only (6890 vertices per frame)
+        if want_vertices:                                                   # meshes of the selected hypothesis only (6890 vertices per frame)
             rs["vertices_ref"] = out_ref[1]
             rs["vertices_rst"] = self._feats_to_joints(f_rst0, b_ref, True, orient=o_ref)[1]
         return rs
@@ -1063,6 +1079,8 @@ class MLD(nn.Module):
                 if split != "test":
                     hm["best_index"] = best_index(hm["MPJPE"], keep_mask(hm, split, hm["have_quat"]))
                 self.HypMetric.update(hm, split)
+                if "selected_index" in hm:                                 # TEST.HYP_SELECT medoid
+                    self.SelMetric.update(hm, split, rs_set.get("mesh_metrics"))
             if "mesh_metrics" in rs_set:                                   # TEST.MESH_METRICS
                 if "hyp_metrics" in rs_set:
                     hm = rs_set["hyp_metrics"]
