@@ -578,6 +578,27 @@ size_t seeme_scene_min_dist2_workspace_bytes(int F, int V, int S, int P);   /* 0
 int seeme_scene_min_dist2(const float* verts, const float* scene, const int32_t* scene_of_frame, int F, int V, int S, int P,
                           float* out_d2, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ point-in-mesh test (csrc/collision.hip)
+ * The collision ratio of the EgoHMR tables (egohmr.py:511-538) without the learned occupancy network: a point is inside the closed,
+ * consistently oriented mesh (verts [F,V,3] of frame f, faces [NF,3] shared by all frames) iff |w| >= 0.5, w the winding number:
+ * w(p) = sum over the faces of 2 atan2(a.(b x c), |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|) / 4 pi, a, b, c the corners minus p.
+ * A face with two equal indices or an index outside 0..V-1 contributes 0 and is never read (the caller validates the table once:
+ * the entry points cannot look into device memory without a synchronisation); a corner vector of length 0 makes the face
+ * contribute 0, never NaN.  V <= 10112 (the frame's vertices live in LDS).  A frame whose map entry is negative (or >= S) is skipped.
+ * One lane sums a point's faces in table order: w and the count do not depend on F, on the other frames or on any chunking, bit
+ * for bit.  No allocation, no synchronisation, no atomics.
+ *
+ * seeme_mesh_winding: out_w[f,p] = w of points[points_of_frame[f]][p] around frame f, every point, no prefilter; zeros for a skipped
+ * frame.
+ * seeme_scene_inside_count: out_count[f] = number of the P points of scene[scene_of_frame[f]] that are inside frame f; 0 for a
+ * skipped frame.  Points outside the closed bounding box of the frame's vertices (w = 0) are dropped on the device first and only
+ * the survivors are evaluated; all P may survive, there is no candidate cap.  Workspace 16-byte aligned: the per-slice counts. */
+size_t seeme_scene_inside_count_workspace_bytes(int F, int V, int S, int P);   /* 0 for bad sizes */
+int seeme_scene_inside_count(const float* verts, const int32_t* faces, int NF, const float* scene, const int32_t* scene_of_frame,
+                             int F, int V, int S, int P, int32_t* out_count, void* ws, size_t ws_bytes, void* stream);
+int seeme_mesh_winding(const float* verts, const int32_t* faces, int NF, const float* points, const int32_t* points_of_frame,
+                       int F, int V, int S, int P, float* out_w, void* stream);
+
 /* ------------------------------------------------------------------ ResNet-50 image backbone (csrc/resnet.hip)
  * EgoHMR.models.resnet.ResNet(Bottleneck, [3,4,6,3]) without fc, frozen and in eval mode: proscene.encode_image
  * (prohmr_scene.py:99-100).  Every BatchNorm is folded on the host (float64) into its convolution:

@@ -216,6 +216,9 @@ _SIGNATURES = {
     "seeme_mesh_v2v_frames": (C.c_int, [fp, fp, fp, fp, fp, C.c_int, C.c_int, fp, fp]),
     "seeme_scene_min_dist2_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "seeme_scene_min_dist2": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, C.c_size_t, fp]),
+    "seeme_scene_inside_count_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "seeme_scene_inside_count": (C.c_int, [fp, fp, C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, C.c_size_t, fp]),
+    "seeme_mesh_winding": (C.c_int, [fp, fp, C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp]),
     "seeme_resnet50_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "seeme_resnet50_encode": (C.c_int, [C.POINTER(Resnet50), fp, C.c_int, C.c_int, fp, fp, C.c_size_t, fp]),
     "seeme_resnet_conv": (C.c_int, [C.POINTER(Conv), C.c_int, fp, C.c_int, C.c_int, C.c_int, fp, C.c_int, fp, fp]),

@@ -58,6 +58,8 @@ def build_parser(phase: str) -> argparse.ArgumentParser:
                    help="override TEST.HYP_SELECT: the draw that stands for its sequence when --num_hypotheses > 1 (medoid: label-free)")
     s.add_argument("--mesh_metrics", action="store_true",
                    help="set TEST.MESH_METRICS: PA-MPJPE, V2V and body-scene contact per hypothesis (seeme_amd/mesh_metrics.py)")
+    s.add_argument("--collision_metrics", action="store_true",
+                   help="set TEST.COLLISION_METRICS: share of the scene cloud inside the body per hypothesis (needs a 'scene' condition)")
     return p
 
 
@@ -73,6 +75,8 @@ def load_cfg(args, phase: str):
         cfg.TEST.HYP_SELECT = args.hyp_select
     if getattr(args, "mesh_metrics", False):
         cfg.TEST.MESH_METRICS = True
+    if getattr(args, "collision_metrics", False):
+        cfg.TEST.COLLISION_METRICS = True
     if args.folder:
         cfg.FOLDER = args.folder
     cfg.setdefault("FOLDER", "./experiments")
@@ -271,6 +275,7 @@ def test_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=None
         model.EgoMetric.reset()
         model.HypMetric.reset()
         model.MeshMetric.reset()
+        model.CollMetric.reset()
         model.SelMetric.reset()
         t0 = time.perf_counter()
         with torch.no_grad():
@@ -293,6 +298,8 @@ def test_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=None
             metrics["samples_per_s"] = model.num_hypotheses * metrics["seqs_per_s"]
         if model.mesh_metrics:          # PA-MPJPE / V2V (best and mean over the kept hypotheses) and, with a scene, distance and contact
             metrics.update(model.MeshMetric.compute(D.reduce_sums(model.MeshMetric.sums().to(dev)).cpu()))
+        if model.collision_metrics:     # share of the scene cloud inside the body, over all hypotheses, and for the reference body
+            metrics.update(model.CollMetric.compute(D.reduce_sums(model.CollMetric.sums().to(dev)).cpu()))
         if model.hyp_select == "medoid" and model.num_hypotheses > 1:    # the errors of the label-free choice among the K draws
             metrics.update(model.SelMetric.compute(D.reduce_sums(model.SelMetric.sums().to(dev)).cpu()))
         log.info("Replication %d: %s", rep, json.dumps({k: round(v, 4) for k, v in metrics.items()}))

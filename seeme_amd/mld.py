@@ -41,7 +41,7 @@ from .config import instantiate_from_config
 from .denoiser_autograd import denoiser_forward_torch
 from .hyp_metrics import (K_MAX, HypothesisMetrics, SelectionMetrics, best_index, check_select, hyp_metrics_hip, hyp_pairdist_hip,
                           keep_mask, select_index)
-from .mesh_metrics import MeshMetrics, mesh_metrics_eval
+from .mesh_metrics import COLLISION_HYP, COLLISION_REF, CollisionMetrics, MeshMetrics, check_closed_faces, mesh_metrics_eval
 from .resnet import ResNet50
 from .respointnet import ResnetPointnet
 from .shapes import motion_layout
@@ -373,6 +373,12 @@ class MLD(nn.Module):
         self.mesh_chunk_mb = cfg.TEST.get("MESH_CHUNK_MB", 256)
         if isinstance(self.mesh_chunk_mb, bool) or not isinstance(self.mesh_chunk_mb, (int, float)) or not self.mesh_chunk_mb > 0:
             raise ValueError(f"TEST.MESH_CHUNK_MB must be a positive number of MiB, got {self.mesh_chunk_mb!r}")
+        # body-scene collision ratio per hypothesis (point-in-mesh test, seeme_amd/mesh_metrics.py); independent of TEST.MESH_METRICS
+        self.collision_metrics = cfg.TEST.get("COLLISION_METRICS", False)
+        if not isinstance(self.collision_metrics, bool):
+            raise ValueError(f"TEST.COLLISION_METRICS must be true or false, got {self.collision_metrics!r}")
+        if self.collision_metrics and "scene" not in self.condition:
+            raise ValueError("TEST.COLLISION_METRICS needs the scene cloud, and model.condition has no 'scene': it would report nothing")
         self.hip_backward = cfg.TRAIN.get("HIP_BACKWARD", True)   # hand-written backward of the denoiser chain (one head)
         self.hip_vae_backward = cfg.TRAIN.get("HIP_VAE_BACKWARD", True)   # stage 1: hand-written VAE backward (vae_train.py)
         self.hip_glue = cfg.TRAIN.get("HIP_GLUE", True)           # ... and of everything around it (stage2_glue.py); needs HIP_BACKWARD
@@ -390,6 +396,11 @@ class MLD(nn.Module):
             self.smpl_model = SMPL(model_path=cfg.model.smpl_path, batch_size=cfg.TRAIN.BATCH_SIZE, gender="neutral")
         for p in self.smpl_model.parameters():
             p.requires_grad = False
+        if self.collision_metrics:
+            try:
+                check_closed_faces(self.smpl_model.faces_tensor, int(self.smpl_model.v_template.shape[0]))
+            except ValueError as e:
+                raise ValueError(f"TEST.COLLISION_METRICS: smpl_model.faces_tensor is not a closed mesh: {e}") from e
 
         self.vae_type = cfg.model.get("vae_type", None) or \
             cfg.model.motion_vae.target.split(".")[-1].lower().replace("vae", "")      # mld.py:174-179
@@ -428,6 +439,7 @@ class MLD(nn.Module):
         self.EgoMetric = EgoMetrics()
         self.HypMetric = HypothesisMetrics()
         self.MeshMetric = MeshMetrics()
+        self.CollMetric = CollisionMetrics()
         self.SelMetric = SelectionMetrics()
         self.do_classifier_free_guidance = self.guidance_scale > 1.0
         self.renorm = datamodule.renorm if datamodule is not None else (lambda x: x)
@@ -865,16 +877,37 @@ class MLD(nn.Module):
               "list_names": {}, "lat_t": z}
         if want_vertices:
             rs["vertices_ref"], rs["vertices_rst"] = out_ref[1], out_rst[1]
-        if self.mesh_metrics:
-            rs["mesh_metrics"] = self._mesh_metrics(f_rst, f_ref, b_ref, o_rst, lengths, 1, scene)
+        self._add_mesh_results(rs, f_rst, f_ref, b_ref, o_rst, lengths, 1, scene)
         return rs
 
-    def _mesh_metrics(self, f_rst, f_ref, b_ref, orient, lengths, K, scene):
+    def _mesh_metrics(self, f_rst, f_ref, b_ref, orient, lengths, K, scene, mesh=True, collision=False):
         """TEST.MESH_METRICS: PA_MPJPE, V2V [B,K] and, with a scene in the batch, SCENE_DIST, CONTACT_RATIO [B,K] and their _REF
-        forms [B] (seeme_amd.mesh_metrics.mesh_metrics_eval: posed and measured in chunks of TEST.MESH_CHUNK_MB MiB of vertices)."""
+        forms [B] (seeme_amd.mesh_metrics.mesh_metrics_eval: posed and measured in chunks of TEST.MESH_CHUNK_MB MiB of vertices).
+        collision: COLLISION_RATIO, COLLISION_FRAMES [B,K] and their _REF forms [B] as well, from the same posed chunks; mesh False
+        leaves the first group out."""
         pose = lambda feats, betas, o: self._feats_to_joints(feats, betas, True, orient=o)
+        if collision and scene is None:
+            raise ValueError("TEST.COLLISION_METRICS: the batch carries no scene cloud")
         return mesh_metrics_eval(pose, f_rst, f_ref, b_ref, orient, lengths, K, scene=scene, chunk_mb=self.mesh_chunk_mb,
-                                 num_vertices=int(self.smpl_model.v_template.shape[0]))
+                                 num_vertices=int(self.smpl_model.v_template.shape[0]),
+                                 faces=self.smpl_model.faces_tensor if collision else None, mesh=mesh)
+
+    def _collision_metrics(self, f_rst, f_ref, b_ref, orient, lengths, K, scene):
+        """TEST.COLLISION_METRICS alone: the four collision keys."""
+        return self._mesh_metrics(f_rst, f_ref, b_ref, orient, lengths, K, scene, mesh=False, collision=True)
+
+    def _add_mesh_results(self, rs, f_rst, f_ref, b_ref, orient, lengths, K, scene):
+        """rs['mesh_metrics'] under TEST.MESH_METRICS, rs['collision_metrics'] under TEST.COLLISION_METRICS; one pass over the posed
+        chunks serves both."""
+        if not (self.mesh_metrics or self.collision_metrics):
+            return
+        out = self._mesh_metrics(f_rst, f_ref, b_ref, orient, lengths, K, scene, mesh=self.mesh_metrics,
+                                 collision=self.collision_metrics)
+        names = COLLISION_HYP + COLLISION_REF
+        if self.mesh_metrics:
+            rs["mesh_metrics"] = {n: v for n, v in out.items() if n not in names}
+        if self.collision_metrics:
+            rs["collision_metrics"] = {n: out[n] for n in names}
 
     # ------------------------------------------------------------------ K hypotheses per sequence in one pass
     MAX_SAMPLE_ROWS = 512          # the largest sampling batch that has a cluster plan (one CU per sample above it)
@@ -1046,8 +1079,7 @@ class MLD(nn.Module):
               "orientation_quat_int": quat(f_int_r), "joints_interactee_gt": joints_int_gt, "lengths": lengths,
               "list_names": {}, "lat_t": pick(z.view(B, K, -1))[None],
               "joints_rst_all": joints_all, "m_rst_all": f_rst.view(B, K, min_len, -1), "lat_t_all": z, "hyp_metrics": hm}
-        if self.mesh_metrics:
-            rs["mesh_metrics"] = self._mesh_metrics(f_rst, f_ref, b_ref, o_ref, lengths, K, scene)
+        self._add_mesh_results(rs, f_rst, f_ref, b_ref, o_ref, lengths, K, scene)
         if want_vertices:                                                   # meshes of the selected hypothesis only (6890 vertices per frame)
             rs["vertices_ref"] = out_ref[1]
             rs["vertices_rst"] = self._feats_to_joints(f_rst0, b_ref, True, orient=o_ref)[1]
@@ -1090,6 +1122,8 @@ class MLD(nn.Module):
                     per = EgoMetrics.per_sequence(rs_set["joints_rst"], rs_set["joints_ref"], rs_set["lengths"], q_rst, q_ref)
                     keep = keep_mask({k: v[:, None] for k, v in per.items()}, split, q_rst is not None and q_ref is not None)
                 self.MeshMetric.update(rs_set["mesh_metrics"], keep)
+            if "collision_metrics" in rs_set:                              # TEST.COLLISION_METRICS
+                self.CollMetric.update(rs_set["collision_metrics"])
         if split == "test":
             return rs_set["joints_rst"]
         return loss
