@@ -393,6 +393,40 @@ int seeme_adamw_step_dev(const void* chunks, int n_chunks, void* const* params, 
                          void* const* exp_avg_sq, const float* step_lr, double beta1, double beta2, double eps,
                          double weight_decay, void* stream);
 
+/* The same update with the training loop's two options in the same pass (seeme_amd/optim.py: FusedAdamWStep with ema_decay /
+ * grad_clip_norm; the reference has neither, Lightning's gradient_clip_val and an EMA callback are what a user would add).
+ * Per element, in fp32: g' = g * grad_scale[0] (skipped when grad_scale is NULL; g is read and never written); the four AdamW
+ * lines of seeme_adamw_step on g'; e += (p_new - e) * (1 - d_t) (skipped when ema is NULL), with
+ * d_t = ema_warmup ? min(ema_decay, (1 + t) / (10 + t)) : ema_decay, t = the 1-based count of this update, formed in double: on
+ * the host from `step` when step_lr is NULL, in the kernel from step_lr[0] otherwise.  With ema == NULL and grad_scale == NULL
+ * the results are the bits of seeme_adamw_step / seeme_adamw_step_dev. */
+typedef struct {
+    const void* chunks;               /* device array of {int tensor, int count, int64 offset} */
+    int n_chunks;
+    void* const* params;              /* device arrays of per-tensor base pointers */
+    const void* const* grads;
+    void* const* exp_avg;
+    void* const* exp_avg_sq;
+    void* const* ema;                 /* NULL: no EMA shadow */
+    const float* step_lr;             /* device {step, lr}; NULL: the host fields lr and step */
+    double lr, step;
+    double beta1, beta2, eps, weight_decay;
+    double ema_decay;                 /* d, 0 <= d < 1 */
+    int ema_warmup;                   /* 0 or 1 */
+    const float* grad_scale;          /* device float (seeme_grad_norm's out + 1); NULL: 1 */
+} SeemeAdamWEx;
+int seeme_adamw_step_ex(const SeemeAdamWEx* a, void* stream);
+int seeme_adamw_ex_bytes(void);
+
+/* Global L2 norm of the gradients behind the same chunk table and pointer table, and the clipping scale of
+ * torch.nn.utils.clip_grad_norm_: out[0] = sqrt(sum g^2), out[1] = min(1, max_norm / (out[0] + 1e-6)); a non-finite norm
+ * propagates as it does there.  Two launches: one workgroup per chunk sums the squares in double (per lane, then the lane sums
+ * in a fixed order) into ws[chunk]; one workgroup adds the partials in chunk order.  No atomics and no host read: equal inputs
+ * give equal bits, and both launches can sit in a captured step.  ws: 8-byte aligned, seeme_grad_norm_workspace_bytes(n_chunks). */
+size_t seeme_grad_norm_workspace_bytes(int n_chunks);
+int seeme_grad_norm(const void* chunks, int n_chunks, const void* const* grads, double max_norm, float* out /* {norm, scale} */,
+                    void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ stage-2 training step: the work around the chain
  * Replaces, for MLD.train_diffusion_forward / _diffusion_process (mld/models/modeltype/mld.py:582-631,887-1017), the
  * PyTorch ops (and their autograd backward) that build the chain's inputs: posterior rsample (mld_vae.py:186-193),

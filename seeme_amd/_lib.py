@@ -138,6 +138,13 @@ class GlueMid(C.Structure):
                 ("g_tn_w", fp * 5), ("g_tn_b", fp * 5), ("dcond", fp), ("dea", fp), ("deb", fp), ("emb", fp), ("demb", fp)]
 
 
+class AdamWEx(C.Structure):
+    _fields_ = [("chunks", fp), ("n_chunks", C.c_int), ("params", fp), ("grads", fp), ("exp_avg", fp), ("exp_avg_sq", fp),
+                ("ema", fp), ("step_lr", fp), ("lr", C.c_double), ("step", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double), ("weight_decay", C.c_double), ("ema_decay", C.c_double), ("ema_warmup", C.c_int),
+                ("grad_scale", fp)]
+
+
 RESNET_FP32, RESNET_BF16 = 0, 1
 IMG_F32_NCHW, IMG_U8_NHWC = 0, 1
 RESNET50_NCONV = 53
@@ -199,6 +206,10 @@ _SIGNATURES = {
     "seeme_adamw_step": (C.c_int, [fp, C.c_int, fp, fp, fp, fp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                    C.c_double, fp]),
     "seeme_adamw_step_dev": (C.c_int, [fp, C.c_int, fp, fp, fp, fp, fp, C.c_double, C.c_double, C.c_double, C.c_double, fp]),
+    "seeme_adamw_step_ex": (C.c_int, [C.POINTER(AdamWEx), fp]),
+    "seeme_adamw_ex_bytes": (C.c_int, []),
+    "seeme_grad_norm_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "seeme_grad_norm": (C.c_int, [fp, C.c_int, fp, C.c_double, fp, fp, C.c_size_t, fp]),
     "seeme_geometry": (C.c_int, [C.c_int, fp, fp, C.c_int, fp]),
     "seeme_renorm": (C.c_int, [fp, fp, fp, fp, C.c_long, C.c_int, fp]),
     "seeme_pointnet_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),

@@ -6,7 +6,8 @@ flat-bucket gradient all-reduce per step, checkpoints in Lightning's ``{"state_d
 ``<FOLDER>/<model_type>/<NAME>/checkpoints/epoch=<n>.ckpt`` (train.py:114-123), resume from the newest
 ``epoch=*.ckpt`` of ``TRAIN.RESUME`` (train.py:26-53), strict load of the ``vae.*`` sub-dict for stage 2
 (train.py:155-167), strict full load for testing (test.py:111-113), metrics summed over ranks and written
-to ``metrics_<time>.json`` (test.py:136-152).
+to ``metrics_<time>.json`` (test.py:136-152), a validation pass every ``LOGGER.VAL_EVERY_STEPS`` epochs (train.py:142-148) with
+``checkpoints/best.ckpt``, and the EMA weights / gradient clipping of ``seeme_amd.optim``.
 
 The argument surface is the reference's (mld/config.py:35-65: --cfg --cfg_assets --batch_size --device
 --nodebug --dir) plus loop bounds for the synthetic data module: the EgoBody / GIMO datasets are
@@ -16,6 +17,7 @@ licence-gated: ``--data_root`` points ``seeme_amd.data.EgoDataModule`` at a dire
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import logging
 import os
@@ -60,6 +62,12 @@ def build_parser(phase: str) -> argparse.ArgumentParser:
                    help="set TEST.MESH_METRICS: PA-MPJPE, V2V and body-scene contact per hypothesis (seeme_amd/mesh_metrics.py)")
     s.add_argument("--collision_metrics", action="store_true",
                    help="set TEST.COLLISION_METRICS: share of the scene cloud inside the body per hypothesis (needs a 'scene' condition)")
+    t = p.add_argument_group("training loop (seeme_amd/optim.py, INTEGRATION.md J)")
+    t.add_argument("--ema_decay", type=float, default=None, help="override TRAIN.EMA_DECAY (0 = no EMA of the weights)")
+    t.add_argument("--grad_clip", type=float, default=None, help="override TRAIN.GRAD_CLIP_NORM (0 = no gradient-norm clipping)")
+    t.add_argument("--val_every", type=int, default=None, help="override LOGGER.VAL_EVERY_STEPS: validate every N epochs (0 = never)")
+    t.add_argument("--val_batches", type=int, default=4, help="synthetic data: validation batches per pass and rank")
+    t.add_argument("--use_ema", action="store_true", help="set TEST.USE_EMA: evaluate the checkpoint's ema_state_dict")
     return p
 
 
@@ -77,6 +85,16 @@ def load_cfg(args, phase: str):
         cfg.TEST.MESH_METRICS = True
     if getattr(args, "collision_metrics", False):
         cfg.TEST.COLLISION_METRICS = True
+    if getattr(args, "ema_decay", None) is not None:
+        cfg.TRAIN.EMA_DECAY = args.ema_decay
+    if getattr(args, "grad_clip", None) is not None:
+        cfg.TRAIN.GRAD_CLIP_NORM = args.grad_clip
+    if getattr(args, "val_every", None) is not None:
+        if args.val_every < 0:
+            raise ValueError("--val_every must be >= 0 (0 = never)")
+        cfg.LOGGER.VAL_EVERY_STEPS = args.val_every
+    if getattr(args, "use_ema", False):
+        cfg.TEST.USE_EMA = True
     if args.folder:
         cfg.FOLDER = args.folder
     cfg.setdefault("FOLDER", "./experiments")
@@ -105,11 +123,24 @@ def make_logger(cfg, phase: str, rank: int) -> logging.Logger:
 
 
 # ----------------------------------------------------------------------------- checkpoints (Lightning layout)
-def save_checkpoint(path: str, model, epoch: int, global_step: int) -> None:
+BEST_CKPT = "best.ckpt"            # the checkpoint of the best validation MPJPE so far; not an epoch=<n>.ckpt, so resume ignores it
+
+
+def save_checkpoint(path: str, model, epoch: int, global_step: int, monitor: Optional[Dict] = None) -> None:
+    """"state_dict" is always the RAW weights (reference tooling loads the file unchanged); with TRAIN.EMA_DECAY on the EMA
+    weights of the trainable tensors travel beside them as "ema_state_dict", under the same names."""
     os.makedirs(os.path.dirname(path), exist_ok=True)
     obj = {"epoch": epoch, "global_step": global_step, "pytorch-lightning_version": "seeme-amd",
            "state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()},
            "optimizer_states": [model.optimizer.state_dict()] if model.optimizer is not None else []}
+    if getattr(model, "ema_decay", 0.0) > 0.0 and model.optimizer is not None:
+        obj["ema_state_dict"] = {k: v.detach().cpu() for k, v in model.ema_state_dict().items()}
+    if monitor is not None:
+        obj["monitor"] = dict(monitor)
+    # where this process's random streams stand: a resumed single-process run then draws what the uninterrupted run would have drawn
+    obj["rng_state"] = {"cpu": torch.get_rng_state()}
+    if torch.cuda.is_available() and torch.cuda.is_initialized():
+        obj["rng_state"]["cuda"] = torch.cuda.get_rng_state()
     tmp = path + ".tmp"
     torch.save(obj, tmp)
     os.replace(tmp, path)
@@ -176,6 +207,54 @@ def _with_image(cfg):
     return "crops" if bool(cfg.model.get("image_backbone", False)) else True
 
 
+def overlay_ema(model, ck: Dict, path: str) -> int:
+    """TEST.USE_EMA: the checkpoint's EMA weights over the (strictly loaded) raw ones."""
+    ema = ck.get("ema_state_dict")
+    if not ema:
+        raise ValueError(f"--use_ema / TEST.USE_EMA: {path} has no ema_state_dict (it was trained with TRAIN.EMA_DECAY 0)")
+    missing, unexpected = model.load_state_dict(ema, strict=False)
+    if unexpected:
+        raise ValueError(f"--use_ema: {path}: ema_state_dict has entries the model does not: {unexpected}")
+    return len(ema)
+
+
+def validate(model, dm, cfg, args, dev, rank: int, ws: int) -> Optional[Dict]:
+    """One validation pass (what Lightning runs every check_val_every_n_epoch, train.py:142-148): model.validation_step over the
+    'val' split -- files: dm.iterate("val", EVAL.BATCH_SIZE); synthetic: --val_batches batches from an index range of their own --
+    on the EMA weights when TRAIN.EMA_DECAY is on, metrics and losses summed over the ranks.  The pass runs on a forked random
+    stream seeded from SEED_VALUE: it draws the same noise every time and leaves the training stream where it was.  None when
+    the data has no 'val' split."""
+    if hasattr(dm, "iterate") and "val" not in getattr(dm, "splits", {"val": None}):
+        return None
+    B = int(cfg.EVAL.BATCH_SIZE if args.batch_size is None else args.batch_size)
+    was_training = model.training
+    model.eval()
+    model.EgoMetric.reset()
+    model.losses["val"].reset()
+    scope = model.ema_scope() if model.ema_decay > 0.0 else contextlib.nullcontext()
+    try:
+        with torch.random.fork_rng(devices=[dev]), torch.no_grad(), scope:
+            torch.manual_seed(int(cfg.SEED_VALUE) * 7919 + 104729 + rank)
+            if hasattr(dm, "iterate"):
+                batches = dm.iterate("val", B, rank=rank, world=ws)
+            else:
+                batches = (dm.batch(B, idx=20_000_000 + it * ws + rank, with_scene=_with_scene(cfg), split="val",
+                                    with_image=_with_image(cfg)) for it in range(args.val_batches))
+            for it, batch in enumerate(batches):
+                model.validation_step(batch, it)
+            sums = D.reduce_sums(model.EgoMetric.sums().to(dev)).cpu()
+            metrics = model.EgoMetric.compute(sums)
+            lsum = model.losses["val"]
+            names = sorted(lsum.sums)
+            vec = D.reduce_sums(torch.stack([torch.as_tensor(lsum.sums[k], dtype=torch.float32, device=dev) for k in names] +
+                                            [torch.as_tensor(float(lsum.count), dtype=torch.float32, device=dev)])).cpu()
+            n = max(float(vec[-1]), 1.0)
+            metrics.update({f"loss_{k}": float(vec[i]) / n for i, k in enumerate(names)})
+    finally:
+        model.train(was_training)
+    return {k: float(v) for k, v in metrics.items()}
+
+
 # ----------------------------------------------------------------------------- train
 def train_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=None) -> Dict:
     args = build_parser("train").parse_args(argv)
@@ -209,11 +288,29 @@ def train_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=Non
         if ck.get("optimizer_states"):
             model.optimizer.load_state_dict(ck["optimizer_states"][0])
         log.info("Resuming after epoch %d (step %d)", start_epoch - 1, global_step)
+        rng = ck.get("rng_state")
+        if rng and ws == 1:            # (several ranks: only rank 0's streams are in the file; every rank restarts from its seed)
+            torch.set_rng_state(rng["cpu"])
+            if "cuda" in rng:
+                torch.cuda.set_rng_state(rng["cuda"], dev)
+        if model.ema_decay > 0.0:
+            if ck.get("ema_state_dict"):
+                model.load_ema_state_dict(ck["ema_state_dict"], strict=True)
+            else:                      # (the shadows are copies of the loaded weights: configure_optimizers made them)
+                log.info("%s has no ema_state_dict: the EMA starts from the loaded weights", resume_ckpt)
 
     B = int(cfg.TRAIN.BATCH_SIZE)
     end_epoch = int(args.epochs if args.epochs is not None else cfg.TRAIN.END_EPOCH)
     save_every = max(1, int((cfg.get("LOGGER") or {}).get("SACE_CHECKPOINT_EPOCH", 1)))
     ckpt_dir = os.path.join(cfg.FOLDER_EXP, "checkpoints")
+    val_every = int((cfg.get("LOGGER") or {}).get("VAL_EVERY_STEPS", 0) or 0)
+    best, last_val, val_skipped = None, {}, False
+    best_path = os.path.join(ckpt_dir, BEST_CKPT)
+    if resume_ckpt and os.path.exists(os.path.join(cfg.TRAIN.RESUME, "checkpoints", BEST_CKPT)):
+        mon = read_checkpoint(os.path.join(cfg.TRAIN.RESUME, "checkpoints", BEST_CKPT)).get("monitor")
+        if mon:
+            best = {"epoch": int(mon["epoch"]), "MPJPE": float(mon["MPJPE"])}
+            log.info("best so far: %s", json.dumps(best))
     log.info("stage %s, conditions %s, batch %d per GPU x %d GPU(s), epochs %d..%d", cfg.TRAIN.STAGE,
              list(cfg.model.condition), B, ws, start_epoch, end_epoch - 1)
     last = {}
@@ -239,6 +336,24 @@ def train_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=Non
         sums = model.losses["train"].compute()
         last = {"epoch": epoch, "step": global_step, "seqs_per_s": round(ws * B * n_it / dt, 1),
                 **{k: round(v, 6) for k, v in sums.items()}}
+        if model.grad_clip_norm > 0.0 and model.last_grad_norm is not None:
+            last["grad_norm"] = round(float(model.last_grad_norm[0]), 6)        # of the epoch's last step; the device is idle here
+        if val_every > 0 and (epoch + 1) % val_every == 0 and not val_skipped:
+            val = validate(model, dm, cfg, args, dev, rank, ws)
+            if val is None:
+                val_skipped = True
+                log.info("the data has no 'val' split: validation is skipped")
+            else:
+                last_val = {f"val_{k}": round(v, 6) for k, v in val.items()}
+                log.info("val epoch %d: %s", epoch, json.dumps(last_val))
+                if val["MPJPE"] == val["MPJPE"] and (best is None or val["MPJPE"] < best["MPJPE"]):
+                    best = {"epoch": epoch, "MPJPE": float(val["MPJPE"])}
+                    if rank == 0:
+                        save_checkpoint(best_path, model, epoch, global_step, monitor=best)
+                        log.info("checkpoint %s (validation MPJPE %.6f)", best_path, best["MPJPE"])
+        last.update(last_val)
+        if best is not None:
+            last["best"] = dict(best)
         log.info("epoch %d: %s", epoch, json.dumps(last))
         if rank == 0 and ((epoch + 1) % save_every == 0 or epoch + 1 == end_epoch):
             path = os.path.join(ckpt_dir, f"epoch={epoch}.ckpt")
@@ -267,7 +382,13 @@ def test_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=None
     if not ckpt:
         raise ValueError("TEST.CHECKPOINTS (or --checkpoint) is required")
     log.info("Loading checkpoints from %s", ckpt)
-    model.load_state_dict(read_checkpoint(ckpt)["state_dict"])        # strict, test.py:111-113
+    ck = read_checkpoint(ckpt)
+    model.load_state_dict(ck["state_dict"])                           # strict, test.py:111-113
+    use_ema = cfg.TEST.get("USE_EMA", False)
+    if not isinstance(use_ema, bool):
+        raise ValueError(f"TEST.USE_EMA must be true or false, got {use_ema!r}")
+    if use_ema:
+        log.info("EMA weights over %d tensors", overlay_ema(model, ck, ckpt))
     model = model.to(dev).eval()
     B = int(cfg.TEST.BATCH_SIZE if args.batch_size is None else args.batch_size)
     all_metrics: Dict[str, List[float]] = {}

@@ -224,3 +224,204 @@ extern "C" int seeme_adamw_step_dev(const void* chunks, int n_chunks, void* cons
                        weight_decay);
     return seeme_check_launch("k_adamw<dev>");
 }
+
+// ---------------------------------------------------------------------------------------------
+// The training loop's extras on the same chunk table: gradient-norm clipping and an exponential moving average (EMA) of the
+// weights.  seeme_grad_norm leaves {norm, scale} in device memory; k_adamw_ex multiplies every gradient by that scale on the
+// way in (g itself is never written) and carries the EMA shadow e as a fifth stream of the one pass: 9 streams instead of 7,
+// no second launch train, no host read anywhere -- both sit in a captured training step.
+struct AdamWExArgs {
+    const AdamWChunk* chunks;
+    float* const* ps; const float* const* gs; float* const* ms; float* const* vs; float* const* es;
+    const float* dev;          // {step, lr} (DEV)
+    const float* gscale;       // NULL: 1
+    float decay, one_minus_beta1, beta2, one_minus_beta2, step_size, sqrt_bias_c2, eps, one_minus_ema;
+    double beta1d, beta2d, wd, ema_decay;
+    int ema_warmup;
+};
+
+// d_t = warm-up ? min(d, (1 + t) / (10 + t)) : d, t = the 1-based count of this update
+__host__ __device__ static inline double ema_decay_at(double d, int warmup, double t) {
+    const double w = (1.0 + t) / (10.0 + t);
+    return (warmup && w < d) ? w : d;
+}
+
+template <bool DEV, bool EMA>
+__global__ __launch_bounds__(256) void k_adamw_ex(const AdamWExArgs a) {
+    float decay = a.decay, step_size = a.step_size, sqrt_bias_c2 = a.sqrt_bias_c2, one_minus_ema = a.one_minus_ema;
+    if (DEV) {
+        const double step = (double)a.dev[0], lr = (double)a.dev[1];
+        decay = (float)(1.0 - lr * a.wd);
+        step_size = (float)(lr / (1.0 - pow(a.beta1d, step)));
+        sqrt_bias_c2 = (float)sqrt(1.0 - pow(a.beta2d, step));
+        if (EMA) one_minus_ema = (float)(1.0 - ema_decay_at(a.ema_decay, a.ema_warmup, step));
+    }
+    const float one_minus_beta1 = a.one_minus_beta1, beta2 = a.beta2, one_minus_beta2 = a.one_minus_beta2, eps = a.eps;
+    const float gsc = a.gscale ? *a.gscale : 1.0f;
+    const AdamWChunk ch = a.chunks[blockIdx.x];
+    float* __restrict__ p = a.ps[ch.tensor] + ch.offset;
+    const float* __restrict__ g = a.gs[ch.tensor] + ch.offset;
+    float* __restrict__ m = a.ms[ch.tensor] + ch.offset;
+    float* __restrict__ v = a.vs[ch.tensor] + ch.offset;
+    float* __restrict__ e = EMA ? a.es[ch.tensor] + ch.offset : nullptr;
+    // The fused multiply-adds are written out, in the forms the compiler chose for k_adamw's two paths (they differ: the 16-byte
+    // body forms v as fma(beta2, v, .) and p as fma(decay, p, .), the scalar loops as fma(1 - beta2, g g, .) and fma(-step_size, q, .)):
+    // with scale == 1 a clipped step must give the bits of the unclipped one, whatever else the optimiser packs or contracts here.
+    auto scaled = [&](float g0) {
+        float gw = g0 * gsc;                                       // g' = g * scale, rounded as clip_grad_norm_'s mul_ rounds it
+        asm("" : "+v"(gw));                                        // ... and not contracted into the subtraction that follows
+        return gw;
+    };
+    auto upd4 = [&](float& pw, float g0, float& mw, float& vw) {
+        const float gw = scaled(g0);
+        mw = fmaf(one_minus_beta1, gw - mw, mw);
+        vw = fmaf(beta2, vw, one_minus_beta2 * (gw * gw));
+        pw = fmaf(decay, pw, -(step_size * (mw / (sqrtf(vw) / sqrt_bias_c2 + eps))));
+    };
+    auto upd1 = [&](float& pw, float g0, float& mw, float& vw) {
+        const float gw = scaled(g0);
+        mw = fmaf(one_minus_beta1, gw - mw, mw);
+        vw = fmaf(one_minus_beta2, gw * gw, beta2 * vw);
+        pw = fmaf(-step_size, mw / (sqrtf(vw) / sqrt_bias_c2 + eps), decay * pw);
+    };
+    auto lerp = [&](float& ew, float pw) { ew = fmaf(pw - ew, one_minus_ema, ew); };     // e.lerp_(p_new, 1 - d_t)
+    size_t al = reinterpret_cast<size_t>(p) | reinterpret_cast<size_t>(g) | reinterpret_cast<size_t>(m) | reinterpret_cast<size_t>(v);
+    if (EMA) al |= reinterpret_cast<size_t>(e);
+    auto one = [&](int i) {
+        float pw = p[i], mw = m[i], vw = v[i];
+        const float gw = g[i];
+        float ew = EMA ? e[i] : 0.f;
+        upd1(pw, gw, mw, vw);
+        p[i] = pw; m[i] = mw; v[i] = vw;
+        if (EMA) { lerp(ew, pw); e[i] = ew; }
+    };
+    if ((al & 15) == 0) {
+        const int n4 = ch.count >> 2;
+        for (int i = threadIdx.x; i < n4; i += 256) {
+            // all loads of the iteration are issued before the first use: 4 (5) x 16 B per lane in flight
+            float4 pw = reinterpret_cast<float4*>(p)[i], mw = reinterpret_cast<float4*>(m)[i], vw = reinterpret_cast<float4*>(v)[i];
+            const float4 gw = reinterpret_cast<const float4*>(g)[i];
+            float4 ew = EMA ? reinterpret_cast<float4*>(e)[i] : float4{0.f, 0.f, 0.f, 0.f};
+            upd4(pw.x, gw.x, mw.x, vw.x); upd4(pw.y, gw.y, mw.y, vw.y); upd4(pw.z, gw.z, mw.z, vw.z); upd4(pw.w, gw.w, mw.w, vw.w);
+            reinterpret_cast<float4*>(p)[i] = pw; reinterpret_cast<float4*>(m)[i] = mw; reinterpret_cast<float4*>(v)[i] = vw;
+            if (EMA) {
+                lerp(ew.x, pw.x); lerp(ew.y, pw.y); lerp(ew.z, pw.z); lerp(ew.w, pw.w);
+                reinterpret_cast<float4*>(e)[i] = ew;
+            }
+        }
+        for (int i = (n4 << 2) + threadIdx.x; i < ch.count; i += 256) one(i);
+    } else {
+        for (int i = threadIdx.x; i < ch.count; i += 256) one(i);
+    }
+}
+
+extern "C" int seeme_adamw_ex_bytes(void) { return (int)sizeof(SeemeAdamWEx); }
+
+extern "C" int seeme_adamw_step_ex(const SeemeAdamWEx* x, void* stream) {
+    if (!x) return seeme_fail("adamw_ex: NULL argument struct");
+    if (x->n_chunks <= 0) return 0;
+    if (!x->chunks || !x->params || !x->grads || !x->exp_avg || !x->exp_avg_sq) return seeme_fail("adamw_ex: NULL table");
+    if (!(x->ema_decay >= 0.0 && x->ema_decay < 1.0)) return seeme_fail("adamw_ex: ema_decay must be in [0, 1)");
+    if (!x->step_lr && !(x->step >= 1.0)) return seeme_fail("adamw_ex: step must be >= 1");
+    if (!x->ema && !x->grad_scale)                                 // nothing to add: the launch, and so the bits, of the plain step
+        return x->step_lr ? seeme_adamw_step_dev(x->chunks, x->n_chunks, x->params, x->grads, x->exp_avg, x->exp_avg_sq, x->step_lr,
+                                                 x->beta1, x->beta2, x->eps, x->weight_decay, stream)
+                          : seeme_adamw_step(x->chunks, x->n_chunks, x->params, x->grads, x->exp_avg, x->exp_avg_sq, x->lr, x->beta1,
+                                             x->beta2, x->eps, x->weight_decay, x->step, stream);
+    AdamWExArgs a;
+    a.chunks = (const AdamWChunk*)x->chunks;
+    a.ps = (float* const*)x->params; a.gs = (const float* const*)x->grads;
+    a.ms = (float* const*)x->exp_avg; a.vs = (float* const*)x->exp_avg_sq; a.es = (float* const*)x->ema;
+    a.dev = x->step_lr; a.gscale = x->grad_scale;
+    a.one_minus_beta1 = (float)(1.0 - x->beta1); a.beta2 = (float)x->beta2; a.one_minus_beta2 = (float)(1.0 - x->beta2);
+    a.eps = (float)x->eps;
+    a.beta1d = x->beta1; a.beta2d = x->beta2; a.wd = x->weight_decay; a.ema_decay = x->ema_decay; a.ema_warmup = x->ema_warmup != 0;
+    a.decay = a.step_size = a.sqrt_bias_c2 = a.one_minus_ema = 0.f;
+    if (!x->step_lr) {
+        const double bc1 = 1.0 - pow(x->beta1, x->step), bc2 = 1.0 - pow(x->beta2, x->step);
+        a.decay = (float)(1.0 - x->lr * x->weight_decay);
+        a.step_size = (float)(x->lr / bc1);
+        a.sqrt_bias_c2 = (float)sqrt(bc2);
+        a.one_minus_ema = (float)(1.0 - ema_decay_at(x->ema_decay, a.ema_warmup, x->step));
+    }
+    const dim3 grid((unsigned)x->n_chunks), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (x->step_lr) {
+        if (x->ema) hipLaunchKernelGGL((k_adamw_ex<true, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_adamw_ex<true, false>), grid, block, 0, st, a);
+    } else {
+        if (x->ema) hipLaunchKernelGGL((k_adamw_ex<false, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_adamw_ex<false, false>), grid, block, 0, st, a);
+    }
+    return seeme_check_launch("k_adamw_ex");
+}
+
+// Sum of squares of one chunk in double: every lane adds its own elements in index order, then the 256 lane sums are added by
+// a fixed tree.  No atomics: the same input gives the same bits.
+__global__ __launch_bounds__(256) void k_grad_sumsq(const AdamWChunk* __restrict__ chunks, const float* const* __restrict__ gs,
+                                                    double* __restrict__ partial) {
+    __shared__ double red[256];
+    const AdamWChunk ch = chunks[blockIdx.x];
+    const float* __restrict__ g = gs[ch.tensor] + ch.offset;
+    double s = 0.0;
+    auto sq = [&](float x) { s += (double)x * (double)x; };
+    if ((reinterpret_cast<size_t>(g) & 15) == 0) {
+        const int n4 = ch.count >> 2;
+        for (int i = threadIdx.x; i < n4; i += 256) {
+            const float4 w = reinterpret_cast<const float4*>(g)[i];
+            sq(w.x); sq(w.y); sq(w.z); sq(w.w);
+        }
+        for (int i = (n4 << 2) + threadIdx.x; i < ch.count; i += 256) sq(g[i]);
+    } else {
+        for (int i = threadIdx.x; i < ch.count; i += 256) sq(g[i]);
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+// The partials in chunk order (staged through LDS 256 at a time, added by lane 0), then {norm, scale} with the arithmetic of
+// torch.nn.utils.clip_grad_norm_: scale = clamp(max_norm / (norm + 1e-6), max = 1) in fp32; a NaN or inf norm propagates.
+__global__ __launch_bounds__(256) void k_grad_norm_final(const double* __restrict__ partial, int n, float max_norm,
+                                                         float* __restrict__ out) {
+    __shared__ double tile[256];
+    double s = 0.0;
+    for (int base = 0; base < n; base += 256) {
+        const int i = base + (int)threadIdx.x;
+        tile[threadIdx.x] = i < n ? partial[i] : 0.0;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int cnt = n - base < 256 ? n - base : 256;
+            for (int j = 0; j < cnt; ++j) s += tile[j];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float norm = (float)sqrt(s);
+        const float c = max_norm / (norm + 1e-6f);
+        out[0] = norm;
+        out[1] = c > 1.0f ? 1.0f : c;
+    }
+}
+
+extern "C" size_t seeme_grad_norm_workspace_bytes(int n_chunks) { return n_chunks <= 0 ? 0 : (size_t)n_chunks * sizeof(double); }
+
+extern "C" int seeme_grad_norm(const void* chunks, int n_chunks, const void* const* grads, double max_norm, float* out, void* ws,
+                               size_t ws_bytes, void* stream) {
+    if (n_chunks <= 0) return 0;
+    if (!chunks || !grads || !out) return seeme_fail("grad_norm: NULL argument");
+    if (!(max_norm > 0.0)) return seeme_fail("grad_norm: max_norm must be > 0");
+    if (!ws || ws_bytes < seeme_grad_norm_workspace_bytes(n_chunks)) return seeme_fail("grad_norm: workspace too small");
+    if (reinterpret_cast<size_t>(ws) & 7) return seeme_fail("grad_norm: workspace must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_grad_sumsq, dim3((unsigned)n_chunks), dim3(256), 0, st, (const AdamWChunk*)chunks, (const float* const*)grads,
+                       (double*)ws);
+    int rc;
+    if ((rc = seeme_check_launch("k_grad_sumsq"))) return rc;
+    hipLaunchKernelGGL(k_grad_norm_final, dim3(1), dim3(256), 0, st, (const double*)ws, n_chunks, (float)max_norm, out);
+    return seeme_check_launch("k_grad_norm_final");
+}

@@ -29,6 +29,8 @@ What runs where
 """
 from __future__ import annotations
 
+import contextlib
+
 import inspect
 import time
 from typing import Dict, List, Optional
@@ -379,6 +381,14 @@ class MLD(nn.Module):
             raise ValueError(f"TEST.COLLISION_METRICS must be true or false, got {self.collision_metrics!r}")
         if self.collision_metrics and "scene" not in self.condition:
             raise ValueError("TEST.COLLISION_METRICS needs the scene cloud, and model.condition has no 'scene': it would report nothing")
+        # training-loop options (seeme_amd/optim.py): EMA of the trainable weights and clipping of the global gradient norm; 0 = off
+        from .optim import check_options
+        self.ema_decay, self.grad_clip_norm = check_options(cfg.TRAIN.get("EMA_DECAY", 0.0), cfg.TRAIN.get("GRAD_CLIP_NORM", 0.0),
+                                                            names=("TRAIN.EMA_DECAY", "TRAIN.GRAD_CLIP_NORM"))
+        self.ema_warmup = cfg.TRAIN.get("EMA_WARMUP", True)
+        if not isinstance(self.ema_warmup, bool):
+            raise ValueError(f"TRAIN.EMA_WARMUP must be true or false, got {self.ema_warmup!r}")
+        self._ema_raw = None           # the raw weights while an ema_scope() is open
         self.hip_backward = cfg.TRAIN.get("HIP_BACKWARD", True)   # hand-written backward of the denoiser chain (one head)
         self.hip_vae_backward = cfg.TRAIN.get("HIP_VAE_BACKWARD", True)   # stage 1: hand-written VAE backward (vae_train.py)
         self.hip_glue = cfg.TRAIN.get("HIP_GLUE", True)           # ... and of everything around it (stage2_glue.py); needs HIP_BACKWARD
@@ -457,18 +467,80 @@ class MLD(nn.Module):
                                                        gamma=self.cfg.TRAIN.OPTIM.GAMMA)
             # eager steps update all tensors in one launch (seeme_adamw_step) on this optimiser's own state; the
             # hipGraph-captured step (capturable=True) stays on PyTorch's AdamW
-            self._fused_adamw = None
+            self._fused_adamw = self._torch_adamw = None
+            opts = dict(ema_decay=self.ema_decay, ema_warmup=self.ema_warmup, grad_clip_norm=self.grad_clip_norm)
             if not capturable and bool(self.cfg.TRAIN.get("FUSED_ADAMW", True)) and params and all(p.is_cuda for p in params):
                 from .optim import FusedAdamWStep
-                self._fused_adamw = FusedAdamWStep(self.optimizer)
+                self._fused_adamw = FusedAdamWStep(self.optimizer, **opts)
+            elif self.ema_decay > 0.0 or self.grad_clip_norm > 0.0:
+                from .optim import TorchAdamWStep
+                self._torch_adamw = TorchAdamWStep(self.optimizer, **opts)      # the same three steps in PyTorch operations
         return {"optimizer": self.optimizer}
 
+    def _stepper(self):
+        return getattr(self, "_fused_adamw", None) or getattr(self, "_torch_adamw", None)
+
     def optimizer_update(self):
-        """The AdamW update of the trainable tensors (after backward and the gradient all-reduce)."""
-        if getattr(self, "_fused_adamw", None) is not None:
-            self._fused_adamw.step()
+        """The AdamW update of the trainable tensors (after backward and the gradient all-reduce), with TRAIN.GRAD_CLIP_NORM and
+        TRAIN.EMA_DECAY when they are on."""
+        if self._ema_raw is not None:
+            raise RuntimeError("optimizer step inside ema_scope(): the parameters hold the EMA weights")
+        st = self._stepper()
+        if st is not None:
+            st.step()
         else:
             self.optimizer.step()
+
+    @property
+    def last_grad_norm(self):
+        """{norm, scale} of the last clipped step as a device tensor (None before it, or with TRAIN.GRAD_CLIP_NORM 0): reading a
+        value synchronises, so the training loop reads it at the epoch's end."""
+        st = self._stepper()
+        return st.last_grad_norm if st is not None else None
+
+    # ------------------------------------------------------------------ EMA weights (TRAIN.EMA_DECAY)
+    def _ema_pairs(self):
+        """(name in state_dict(), parameter, shadow) of every trainable tensor."""
+        st = self._stepper()
+        if st is None or self.ema_decay <= 0.0:
+            raise RuntimeError("EMA is off (TRAIN.EMA_DECAY 0, or configure_optimizers() has not run)")
+        st._ensure_shadows()
+        return [(n, p, st.shadow[p]) for n, p in self.named_parameters() if p in st.shadow]
+
+    def ema_state_dict(self):
+        return {n: e for n, _, e in self._ema_pairs()}
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, sd, strict: bool = True):
+        pairs = self._ema_pairs()
+        if strict:
+            missing, unexpected = [n for n, _, _ in pairs if n not in sd], sorted(set(sd) - {n for n, _, _ in pairs})
+            if missing or unexpected:
+                raise RuntimeError(f"load_ema_state_dict: missing {missing}, unexpected {unexpected}")
+        for n, _, e in pairs:
+            if n in sd:
+                if tuple(sd[n].shape) != tuple(e.shape):
+                    raise RuntimeError(f"load_ema_state_dict: {n} has shape {tuple(sd[n].shape)}, expected {tuple(e.shape)}")
+                e.copy_(sd[n])
+
+    @contextlib.contextmanager
+    def ema_scope(self):
+        """The EMA weights in the parameters for the length of the block, the raw weights back on exit (also on an exception).  The
+        copies are in place -- captured graphs and pointer tables keep the parameters' addresses -- and bump the version counters,
+        so the sampling-side weight images rebuild on entry and on exit.  Not re-entrant; no optimiser step inside."""
+        pairs = self._ema_pairs()
+        if self._ema_raw is not None:
+            raise RuntimeError("ema_scope() is not re-entrant")
+        with torch.no_grad():
+            self._ema_raw = [p.detach().clone() for _, p, _ in pairs]
+            try:
+                for _, p, e in pairs:
+                    p.copy_(e)
+                yield self
+            finally:
+                for (_, p, _), raw in zip(pairs, self._ema_raw):
+                    p.copy_(raw)
+                self._ema_raw = None
 
     def trainable_parameters(self):
         return [p for p in self.parameters() if p.requires_grad]
@@ -1238,6 +1310,8 @@ class MLD(nn.Module):
         after AdamW) recorded on the current stream."""
         from . import distributed as D
         self.configure_optimizers()
+        if self._ema_raw is not None:
+            raise RuntimeError("optimizer_step inside ema_scope(): the parameters hold the EMA weights")
         if events is not None:
             events[0].record()
         bucket = self.backward(loss)

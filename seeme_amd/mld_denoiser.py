@@ -532,8 +532,8 @@ class MldDenoiser(nn.Module):
             raise ValueError("condition batch must be B (or 2B with classifier-free guidance)")
         dev = latents.device
         key = (tuple(scheduler.timesteps.tolist()), float(eta), type(scheduler).__name__)
+        self._weights()                      # first: a changed parameter drops the time tables cached for the old weights
         cached = self._table_cache.get(key)
-        self._weights()
         if cached is None:
             tfeat = timestep_features(scheduler.timesteps.cpu(), self.text_encoded_dim, self.flip_sin_to_cos,
                                       self.freq_shift).to(dev)
