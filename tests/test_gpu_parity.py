@@ -161,6 +161,8 @@ def test_denoiser_16bit_weights(dev, wd, tol):
     """16-bit weight images (activations / accumulation stay fp32): error is MEASURED and reported; the 1e-4 gate
     applies to the fp32 image only."""
     g = load_golden("denoiser_N1.npz")
+    # cluster="auto" at B = 3: both runs below are k_den_cluster with 8 CUs per sample, not k_den_sample (test_gpu_exact16.py holds
+    # each 16-bit kernel to the oracle by name, at fp32 tolerance)
     den = make_den(dev, weight_dtype=wd)
     s, c = torch.from_numpy(g["sample"]).to(dev), torch.from_numpy(g["cond"]).to(dev)
     y = den(sample=s, timestep=torch.tensor(501), encoder_hidden_states=c)[0]
@@ -497,7 +499,8 @@ def test_denoiser_multihead_vs_oracle(dev, H):
 @pytest.mark.parametrize("cfg", [False, True])
 def test_sampling_kernel_variants(dev, wd, tol, H, N, cfg):
     """Every compiled variant of the persistent kernel (weight type x CFG pair x one/many condition tokens x
-    folded/unfolded out_proj) against the oracle loop, 6 DDIM steps, B = 3."""
+    folded/unfolded out_proj) against the oracle loop, 6 DDIM steps, B = 3.  (cluster="auto": the H = 1, N = 1, no-CFG rows run
+    k_den_cluster with 8 CUs per sample; every other row runs k_den_sample.  test_gpu_exact16.py covers both by name.)"""
     from seeme_amd.mld_denoiser import MldDenoiser
     den = load_recipe_(MldDenoiser(ablation(), condition=["text", "scene", "interactee"], latent_dim=[1, 256], ff_size=128,
                                    num_layers=5, num_heads=H, weight_dtype=wd)).to(dev).eval()
@@ -576,7 +579,7 @@ def test_pointnet_bf16_vs_fp32(dev):
     tolerance 3e-2 of the output range, reported)."""
     from seeme_amd.respointnet import ResnetPointnet
     pn = load_recipe_(ResnetPointnet(512, 256)).to(dev).eval()
-    pts = torch.from_numpy(np.random.default_rng(4).uniform(-3, 3, (3, 1000, 3)).astype(np.float32)).to(dev)   # ragged: 1000 = 7*128 + 104
+    pts = torch.from_numpy(np.random.default_rng(4).uniform(-3, 3, (3, 1000, 3)).astype(np.float32)).to(dev)   # ragged: 1000 = 3*256 + 232 (256-point tiles)
     ref = pn(pts)
     pn.precision = "bf16"
     got = pn(pts)
@@ -651,6 +654,72 @@ def test_pointnet_bf16_tile_walk(dev):
         pn.precision = "fp32"
         ref = pn(pts[list(probe)].contiguous())
         assert rel_err(got[list(probe)].cpu().numpy(), ref.cpu().numpy()) < 3e-2
+
+
+# ----------------------------------------------------------------------------- bf16 PointNet: the rows at the edge of a tile
+_PN_EDGE_P = [1, 2, 15, 16, 17, 31, 32, 33, 255, 256, 257, 513]     # around the 16-point group, the 32 rows of a wave, the 256-point tile
+_PN = {}
+
+
+def _pointnet(dev):
+    from seeme_amd.respointnet import ResnetPointnet
+    if "pn" not in _PN:
+        _PN["pn"] = load_recipe_(ResnetPointnet(512, 256)).to(dev).eval()
+    return _PN["pn"]
+
+
+def _pn_scenes(P):
+    """B = 2 different scenes whose LAST valid point lies far from the rest."""
+    pts = np.random.default_rng(1000 + P).uniform(-3, 3, (2, P, 3)).astype(np.float32)
+    pts[:, -1] = (12.0, -12.0, 12.0)
+    return pts
+
+
+def _pn_run(pn, precision, pts, dev):
+    pn.precision = precision
+    return pn(torch.from_numpy(pts.copy(order="C")).to(dev))     # (a copy: reversed views have negative strides)
+
+
+@pytest.mark.parametrize("P", _PN_EDGE_P)
+def test_pointnet_bf16_last_valid_point_counts(dev, P):
+    """k_pn_block2 masks the rows past the last valid point of a tile with -inf (rows_valid).  With uniform(-3, 3) data a dropped last point
+    or a zero pad row that leaks into the max moves the output by less than the 3e-2 bf16 bound.  Here the last valid point of each
+    scene is (12, -12, 12): by the oracle alone, dropping it costs at least 0.59 of the output range at every P below, and a zero pad
+    row 0.45 at P = 1 and 0.08 at P = 2."""
+    pn = _pointnet(dev)
+    pts = _pn_scenes(P)
+    ref = _pn_run(pn, "fp32", pts, dev).cpu().numpy()
+    got = _pn_run(pn, "bf16", pts, dev).cpu().numpy()
+    oracle = O.pointnet_forward(recipe_state_dict(shapes.pointnet_shapes()), pts)
+    e, eo = rel_err(got, ref), rel_err(got, oracle)
+    print(f"bf16 PointNet P={P}, far last point: rel err vs fp32 path {e:.3e}, vs oracle {eo:.3e}")
+    assert np.isfinite(got).all()
+    assert rel_err(ref, oracle) < TOL_F32
+    assert e < 3e-2 and eo < 3e-2
+
+
+@pytest.mark.parametrize("P", _PN_EDGE_P)
+def test_pointnet_bf16_point_order_is_irrelevant(dev, P):
+    """The max is exact and the per-point arithmetic does not depend on the row a point sits in: the same scenes with the points
+    reversed, and rolled by one, give bit-identical bf16 output -- the far point visits the first row, the last valid row and the row
+    next to the tile edge."""
+    pn = _pointnet(dev)
+    pts = _pn_scenes(P)
+    got = _pn_run(pn, "bf16", pts, dev)
+    rev = _pn_run(pn, "bf16", pts[:, ::-1], dev)
+    rol = _pn_run(pn, "bf16", np.roll(pts, 1, axis=1), dev)
+    assert torch.equal(got, rev), float((got - rev).abs().max())
+    assert torch.equal(got, rol), float((got - rol).abs().max())
+
+
+def test_pointnet_bf16_one_point_equals_its_copies(dev):
+    """A scene of ONE point equals, bit for bit, the same point repeated 300 times (a full tile and a partial one): pad rows add nothing,
+    copies add nothing."""
+    pn = _pointnet(dev)
+    one = _pn_scenes(1)
+    got = _pn_run(pn, "bf16", one, dev)
+    rep = _pn_run(pn, "bf16", np.repeat(one, 300, axis=1), dev)
+    assert torch.equal(got, rep), float((got - rep).abs().max())
 
 
 def test_vae_fp16_mfma_mode(dev):
