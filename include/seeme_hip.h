@@ -591,6 +591,44 @@ size_t seeme_hyp_pairdist_workspace_bytes(int B, int K, int T);   /* 0 for bad s
 int seeme_hyp_pairdist(const float* jts_pred, const int32_t* lengths, int B, int K, int T, float* dist, int32_t* medoid,
                        void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ a whole recording from overlapping windows (csrc/recording.hip)
+ * A recording of n_frames frames is cut into W windows of T frames that start S = T - O frames apart, 0 <= O and 2*O <= T (no frame
+ * lies in more than two windows): W = 1 for n_frames <= T, else ceil((n_frames - T) / S) + 1; window w starts at w*S and has
+ * min(T, n_frames - w*S) valid frames; windows w and w+1 share the last O frames of w and the first O of w+1.  All windows are in ONE
+ * coordinate frame.  K hypotheses per window, K <= 32.  fp32, no atomics: bitwise reproducible.
+ *
+ * Disagreement of neighbouring windows on their shared frames.  jts [W,K,T,24,3] (metres, 16-byte aligned):
+ * cost[w,i,j] = 1000 x the mean over r = 0..O-1 and the 24 joints of |a - b| (mm), a = hypothesis i of window w at frame T-O+r,
+ * b = hypothesis j of window w+1 at frame r.  No alignment of any kind: the global position is part of what must agree.  cost is
+ * [W-1,K,K]; W = 1 or O = 0 writes nothing and returns success.  Frames outside the overlaps are never read.  The workspace (16-byte
+ * aligned) holds the per-chunk partial sums. */
+size_t seeme_overlap_cost_workspace_bytes(int W, int K, int T, int O);   /* 0 for bad sizes */
+int seeme_overlap_cost(const float* jts, int W, int K, int T, int O, float* cost, void* ws, size_t ws_bytes, void* stream);
+
+/* The path p_0 .. p_{W-1} that minimises sum_w unary[w,p_w] + sum_w cost[w,p_w,p_{w+1}], by dynamic programming.  cost [W-1,K,K],
+ * unary [W,K] or NULL (no unary term).  With d_0[j] = unary[0,j] (0 without unary), d_{w+1}[j] = min_i (d_w[i] + cost[w,i,j]) +
+ * unary[w+1,j], every sum in fp32 in this order; the LOWEST i wins a tie and is the back-pointer, and the lowest j of the smallest
+ * d_{W-1} ends the path.  path [W] int32; seam[w] = cost[w,p_w,p_{w+1}] ([W-1]); total[0] = d_{W-1}[p_{W-1}], the path's sum.  W = 1
+ * gives the argmin of unary (0 without it).  A set of candidates that holds a NaN has no minimum: index 0 and a NaN sum.  The
+ * workspace (4-byte aligned) holds the back-pointers. */
+size_t seeme_path_select_workspace_bytes(int W, int K);                  /* 0 for bad sizes */
+int seeme_path_select(const float* cost, const float* unary, int W, int K, int32_t* path, float* seam, float* total,
+                      void* ws, size_t ws_bytes, void* stream);
+
+/* One motion out of the chosen hypothesis of every window.  feats [W,T,F] renormed features, out [n_frames,F]; W must be the window
+ * plan of (n_frames, T, O).  Frame n lies in window w = min(n / S, W-1) at local frame t = n - w*S; for w >= 1 and t < O it is also
+ * frame t + S of window w-1 and the two are blended with weight u = (t+1)/(O+1) for the LATER window, otherwise it is copied.
+ * layout: SEEME_STITCH_ANGLE F = J x 3 axis-angle values; SEEME_STITCH_ANGLE_TRANSL the same with 3 translation values last
+ * (TRAIN.ABLATION.PREDICT_TRANSL); SEEME_STITCH_ROT6D F = 24 x 6, read as seeme_geometry's SEEME_GEO_ROT6D_PROHMR reads it (a1 = x[0:3],
+ * a2 = x[3:6], Gram-Schmidt) and written back as the first two columns of the blended rotation.  Each joint rotation: unit
+ * quaternion (axis-angle v: (cos(|v|/2), sin(|v|/2) v/|v|); rot6d: of its rotation matrix) -> the later one negated when the dot
+ * product of the two is negative -> slerp, or, when the dot product exceeds SEEME_STITCH_NLERP_DOT, the lerp (1-u) p + u q -> normalised
+ * -> back to the feature's own parameterisation (axis-angle with an angle in [0, pi]).  Translation: a + u (b - a).  Frames past a
+ * window's valid length are never read. */
+enum { SEEME_STITCH_ANGLE = 0, SEEME_STITCH_ANGLE_TRANSL = 1, SEEME_STITCH_ROT6D = 2 };
+#define SEEME_STITCH_NLERP_DOT 0.9995f
+int seeme_stitch_windows(const float* feats, int W, int T, int O, int n_frames, int F, int layout, float* out, void* stream);
+
 /* ------------------------------------------------------------------ per-frame mesh metrics (csrc/mesh_metrics.hip)
  * Frame-level primitives of the EgoHMR tables (test_egohmr.py:463-492, 540-549): one float per frame, fp32 metres in and out, a
  * frame whose map entry is negative is skipped and gets 0; the caller averages over the valid frames of a sequence and chunks the

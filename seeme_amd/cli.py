@@ -441,3 +441,74 @@ def test_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=None
         log.info("Testing done, the metrics are saved to %s", metric_file)
         out["file"] = metric_file
     return out
+
+
+# ----------------------------------------------------------------------------- a recording without labels -> one stitched motion
+def motion_to_smpl(motion: torch.Tensor, data_type: str, transl_in_feats: bool, nb: int) -> Dict[str, torch.Tensor]:
+    """Renormed features [N,F] -> global_orient [N,3], body_pose [N,nb] and transl [N,3] (zeros when the features carry none), axis-
+    angle: 'angle' features are split, 'rot6d' ones (24 x 6, the translation outside them) go through ``geometry.rot6d_to_rotmat`` and
+    ``geometry.rotmat_to_aa_torch``."""
+    from . import geometry as G
+    N = motion.shape[0]
+    if data_type == "rot6d":
+        aa = G.rotmat_to_aa_torch(G.rot6d_to_rotmat(motion[:, :144].reshape(-1, 6).contiguous())).reshape(N, 72)
+        return {"global_orient": aa[:, :3], "body_pose": aa[:, 3:], "transl": torch.zeros(N, 3, device=motion.device)}
+    tr = motion[:, -3:] if transl_in_feats else torch.zeros(N, 3, device=motion.device)
+    return {"global_orient": motion[:, :3], "body_pose": motion[:, 3:3 + nb], "transl": tr}
+
+
+def predict_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=None) -> Dict:
+    """predict.py: a recording .npz (``recording.load_recording``: the interactee's motion, optionally a scene cloud, image features
+    and the wearer's betas -- no wearer labels) -> the stitched SMPL motion of the wearer as an .npz."""
+    import numpy as np
+    from . import recording as R
+    p = build_parser("predict")
+    g = p.add_argument_group("recording")
+    g.add_argument("--input", type=str, required=True, help="recording .npz (INTEGRATION.md K)")
+    g.add_argument("--output", type=str, required=True, help="where the stitched motion goes (.npz)")
+    g.add_argument("--overlap", type=int, default=None, help="override TEST.WINDOW_OVERLAP (frames shared by neighbouring windows)")
+    g.add_argument("--seed", type=int, default=None, help="seed of the draws (default: SEED_VALUE)")
+    g.add_argument("--save_hypotheses", action="store_true", help="also store m_rst_all [W,K,T,F], every window's K hypotheses")
+    p.set_defaults(frames=None)                                         # the window length: MOTION_LENGTH unless --frames says otherwise
+    args = p.parse_args(argv)
+    cfg = load_cfg(args, "test")
+    args.frames = T = int(args.frames or cfg.MOTION_LENGTH)
+    log = make_logger(cfg, "predict", 0)
+    if not torch.cuda.is_available():
+        raise SystemExit("prediction runs on the HIP path: an MI355X is required (no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if args.overlap is not None:
+        cfg.TEST.WINDOW_OVERLAP = args.overlap
+    model, dm = build(cfg, dev, args, datamodule, smpl_model)
+    ckpt = args.checkpoint or cfg.TEST.get("CHECKPOINTS")
+    if not ckpt:
+        raise ValueError("TEST.CHECKPOINTS (or --checkpoint) is required")
+    log.info("Loading checkpoints from %s", ckpt)
+    ck = read_checkpoint(ckpt)
+    model.load_state_dict(ck["state_dict"])
+    if cfg.TEST.get("USE_EMA", False):
+        log.info("EMA weights over %d tensors", overlay_ema(model, ck, ckpt))
+    model = model.to(dev).eval()
+    rec = R.load_recording(args.input)
+    O = model.window_overlap if model.window_overlap is not None else T // 4
+    batch, starts, lengths = R.windows_batch(rec, dm, T, O, tuple(cfg.model.condition), dataset=str(cfg.DATASET_NAME),
+                                             data_type=str(cfg.DATA_TYPE), predict_transl=bool(cfg.TRAIN.ABLATION.PREDICT_TRANSL),
+                                             device=dev)
+    torch.manual_seed(int(cfg.SEED_VALUE) if args.seed is None else args.seed)
+    betas = torch.from_numpy(rec["wearer_betas"]).to(dev) if "wearer_betas" in rec else None
+    out = model.predict_recording(batch, rec["n_frames"], overlap=O, betas=betas)
+    nb = 69 if model.name_dataset == "egobody" else 63
+    res = {k: v.float().cpu().numpy() for k, v in motion_to_smpl(out["motion"], model.data_type, model.transl_in_feats, nb).items()}
+    res.update(joints=out["joints"].cpu().numpy(), window_starts=np.asarray(starts, np.int64), path=out["path"].cpu().numpy(),
+               seam_cost=out["seam_cost"].cpu().numpy())
+    if args.save_hypotheses:
+        res["m_rst_all"] = out["predict"]["m_rst_all"].cpu().numpy()
+    d = os.path.dirname(os.path.abspath(args.output))
+    os.makedirs(d, exist_ok=True)
+    with open(args.output, "wb") as f:                                  # (np.savez would append .npz to a bare name)
+        np.savez(f, **res)
+    log.info("%d frames in %d windows of %d (overlap %d), %d hypotheses each; mean seam cost %.1f mm; written to %s", rec["n_frames"],
+             len(starts), T, O, int(out["predict"]["m_rst_all"].shape[1]),
+             float(out["seam_cost"].mean()) if len(starts) > 1 else 0.0, args.output)
+    return {"file": args.output, "n_frames": rec["n_frames"], "windows": len(starts), "path": out["path"].tolist(),
+            "path_cost": float(out["path_cost"])}

@@ -90,6 +90,39 @@ def load_pickled(path: str):
 
 
 # ----------------------------------------------------------------------------- one split, resident
+def load_time_stats(mean: np.ndarray, std: np.ndarray, rot6d: bool):
+    """The (mean, std) vectors the load-time normalisation of a person applies: the files' own for 'angle'; rot6d assembles the split
+    RAW (zero mean, unit std) and normalises the re-encoded values afterwards (``normalise_rot6d``)."""
+    return (np.zeros(75, np.float32), np.ones(75, np.float32)) if rot6d else (mean[0], std[0])
+
+
+def normalise_person(go, bp, tr, m, s, dataset: str, norm_transl: bool):
+    """One person's zero-padded frames -> (motion [T, 3 + P], transl [T, 3]) as the batches carry them: (x - mean) / std on the
+    global orientation [0, 3) and the body pose [3, 3 + P); on the translation only when it is part of the features
+    (PREDICT_TRANSL with 'angle', :1615), with the statistics at [numdims, +3) for EgoBody and the LAST three for GIMO
+    (:1607-1612, 2360-2364).  The one statement of the rule: ``EgoSequenceSplit`` and ``recording.windows_batch`` both call it."""
+    go_dims, numdims = go.shape[1], go.shape[1] + bp.shape[1]
+    motion = np.concatenate([(go - m[:go_dims]) / s[:go_dims], (bp - m[go_dims:numdims]) / s[go_dims:numdims]], axis=1)
+    if norm_transl:
+        t_lo = numdims if dataset == "egobody" else m.shape[0] - 3
+        tr = (tr - m[t_lo: t_lo + 3]) / s[t_lo: t_lo + 3]
+    return motion, tr
+
+
+def normalise_rot6d(aa: torch.Tensor, length: torch.Tensor, mean: np.ndarray, std: np.ndarray, encode_device=None) -> torch.Tensor:
+    """Raw axis-angle [N,T,P,72] -> normalised rot6d [N,T,P,144] (see ``EgoSequenceSplit._to_rot6d``); length [N] or [N,1]."""
+    dev = torch.device(encode_device) if encode_device is not None else torch.device("cpu")
+    flat = aa.reshape(-1, 3).float().contiguous()
+    if dev.type == "cuda":
+        R = torch.cat([G.aa_to_rotmat(c.to(dev)).cpu() for c in flat.split(1 << 22)])   # 48 MB of axis-angle at a time
+    else:
+        R = G.aa_to_rotmat_torch(flat)
+    r6 = G.rotmat_to_rot6d(R, "diffusion").reshape(*aa.shape[:-1], 144)
+    valid = torch.arange(aa.shape[1])[None, :] < length.reshape(-1, 1)                   # [N,T]
+    r6 = r6 * valid[:, :, None, None].to(r6.dtype)
+    return ((r6 - torch.from_numpy(mean[0, :144])) / torch.from_numpy(std[0, :144])).contiguous()
+
+
 class EgoSequenceSplit:
     """One split of EgoBody (``EgoBodyData3``) or GIMO (``GimoData``), preprocessed once into stacked tensors."""
 
@@ -141,8 +174,7 @@ class EgoSequenceSplit:
         pe_beta = np.zeros((N, T, 1, 10), np.float32) if pe else None
         first_image: List[str] = []
         # rot6d: the split is assembled RAW (axis-angle, zero padded) and converted + normalised once, after the loop
-        m, s = (np.zeros(75, np.float32), np.ones(75, np.float32)) if rot6d else (self.mean[0], self.std[0])
-        t_lo = self.numdims if dataset == "egobody" else m.shape[0] - 3                    # EgoBody: [numdims, +3); GIMO: the last three (:1607-1612, 2360-2364)
+        m, s = load_time_stats(self.mean, self.std, rot6d)
         for i, name in enumerate(names):
             it = load_pickled(os.path.join(d, name))
             ru = it["recording_utils"]
@@ -171,11 +203,7 @@ class EgoSequenceSplit:
                     bp[:L] = np.stack([np.asarray(e["body_pose"], np.float32).reshape(-1)[: self.pose_dim] for e in est])
                     bt = np.stack([np.asarray(e["betas"], np.float32).reshape(10) for e in est])
                 # zero padding comes BEFORE the normalisation, as in the reference (:1524-1546): padded frames are -mean/std
-                motion[i, :, p, : self.go_dims] = (go - m[: self.go_dims]) / s[: self.go_dims]
-                motion[i, :, p, self.go_dims:] = (bp - m[self.go_dims: self.numdims]) / s[self.go_dims: self.numdims]
-                if self.predict_transl and not rot6d:                                          # 'angle' only (:1615)
-                    tr = (tr - m[t_lo: t_lo + 3]) / s[t_lo: t_lo + 3]
-                transl[i, p] = tr
+                motion[i, :, p], transl[i, p] = normalise_person(go, bp, tr, m, s, dataset, self.predict_transl and not rot6d)
                 beta[i, p, :L] = bt
             cols = [np.asarray(ru[k], np.float32).reshape(L, -1) for k in ("fx", "cx", "cy", "center", "scale")]
             utils[i, :L] = np.concatenate(cols, axis=1)                                        # [L, 1+1+1+2+1] (:1584-1586)
@@ -207,15 +235,7 @@ class EgoSequenceSplit:
         the 'diffusion' element order [r00, r01, r10, r11, r20, r21] (utils_egobody/geometry.py:256-262), zeros in the frames past
         the sequence's length (the reference converts first, dataset.py:1376-1416, and zero-pads the converted values, :1524-1546),
         then (x - mean) / std."""
-        flat = aa.reshape(-1, 3).float().contiguous()
-        if self.encode_device.type == "cuda":
-            R = torch.cat([G.aa_to_rotmat(c.to(self.encode_device)).cpu() for c in flat.split(1 << 22)])   # 48 MB of axis-angle at a time
-        else:
-            R = G.aa_to_rotmat_torch(flat)
-        r6 = G.rotmat_to_rot6d(R, "diffusion").reshape(*aa.shape[:-1], 144)
-        valid = torch.arange(aa.shape[1])[None, :] < self.length.reshape(-1, 1)               # [N,T]
-        r6 = r6 * valid[:, :, None, None].to(r6.dtype)
-        return ((r6 - torch.from_numpy(self.mean[0, :144])) / torch.from_numpy(self.std[0, :144])).contiguous()
+        return normalise_rot6d(aa, self.length, self.mean, self.std, self.encode_device)
 
     def _load_image_feats(self, path: str):
         """The feature table of the split and, per sequence, the table rows of its frames (flat, with offsets and counts)."""

@@ -93,3 +93,33 @@ def aa_to_rotmat_torch(theta: torch.Tensor) -> torch.Tensor:
     return torch.stack([w2 + x2 - y2 - z2, 2 * xy - 2 * wz, 2 * wy + 2 * xz,
                         2 * wz + 2 * xy, w2 - x2 + y2 - z2, 2 * yz - 2 * wx,
                         2 * xz - 2 * wy, 2 * wx + 2 * yz, w2 - x2 - y2 + z2], dim=1).view(-1, 3, 3)
+
+
+def rotmat_to_quat_torch(R: torch.Tensor) -> torch.Tensor:
+    """[..., 3, 3] rotation matrices -> [..., 4] unit quaternions (w,x,y,z), plain torch (any device and dtype): the largest of
+    w, x, y, z is taken first (Shepperd), so no branch divides by a small number.  The sign is whatever that branch gives."""
+    m00, m01, m02, m10, m11, m12, m20, m21, m22 = R.reshape(*R.shape[:-2], 9).unbind(-1)
+    root = lambda v: torch.sqrt(v.clamp_min(1e-30)) * 2.0                      # (only the selected branch's value is used)
+    tr = m00 + m11 + m22
+    s0, s1, s2, s3 = root(tr + 1.0), root(1.0 + m00 - m11 - m22), root(1.0 + m11 - m00 - m22), root(1.0 + m22 - m00 - m11)
+    q0 = torch.stack([0.25 * s0, (m21 - m12) / s0, (m02 - m20) / s0, (m10 - m01) / s0], dim=-1)
+    q1 = torch.stack([(m21 - m12) / s1, 0.25 * s1, (m01 + m10) / s1, (m02 + m20) / s1], dim=-1)
+    q2 = torch.stack([(m02 - m20) / s2, (m01 + m10) / s2, 0.25 * s2, (m12 + m21) / s2], dim=-1)
+    q3 = torch.stack([(m10 - m01) / s3, (m02 + m20) / s3, (m12 + m21) / s3, 0.25 * s3], dim=-1)
+    c0, c1, c2 = (tr > 0)[..., None], ((m00 > m11) & (m00 > m22))[..., None], (m11 > m22)[..., None]
+    q = torch.where(c0, q0, torch.where(c1, q1, torch.where(c2, q2, q3)))
+    return q / q.norm(dim=-1, keepdim=True)
+
+
+def quat_to_aa_torch(q: torch.Tensor) -> torch.Tensor:
+    """[..., 4] unit quaternions -> [..., 3] axis-angle with an angle in [0, pi] (q and -q give the same result)."""
+    q = torch.where(q[..., :1] < 0, -q, q)
+    v = q[..., 1:]
+    vn = v.norm(dim=-1, keepdim=True)
+    k = torch.where(vn > 1e-12, 2.0 * torch.atan2(vn, q[..., :1]) / vn.clamp_min(1e-12), torch.full_like(vn, 2.0))
+    return k * v
+
+
+def rotmat_to_aa_torch(R: torch.Tensor) -> torch.Tensor:
+    """[..., 3, 3] rotation matrices -> [M, 3] axis-angle with an angle in [0, pi], plain torch (any device and dtype)."""
+    return quat_to_aa_torch(rotmat_to_quat_torch(R.reshape(-1, 3, 3)))

@@ -368,6 +368,16 @@ class MLD(nn.Module):
         # which of the K > 1 hypotheses stands for its sequence in the keys of a K = 1 result: 'first' (hypothesis 0, today's result) or
         # 'medoid' (smallest total distance to the other draws: seeme_hyp_pairdist; needs no ground truth)
         self.hyp_select = check_select(cfg.TEST.get("HYP_SELECT", "first"), "TEST.HYP_SELECT")
+        # a whole recording (predict_recording): frames shared by neighbouring windows (None: T // 4 of the batch) and the weight of
+        # the medoid term against the seam term when ONE hypothesis per window is chosen (0: seams only)
+        self.window_overlap = cfg.TEST.get("WINDOW_OVERLAP", None)
+        if self.window_overlap is not None and (isinstance(self.window_overlap, bool) or not isinstance(self.window_overlap, int)
+                                                or self.window_overlap < 0):
+            raise ValueError(f"TEST.WINDOW_OVERLAP must be an integer >= 0 (at most half the window), got {self.window_overlap!r}")
+        self.path_medoid_weight = cfg.TEST.get("PATH_MEDOID_WEIGHT", 1.0)
+        if isinstance(self.path_medoid_weight, bool) or not isinstance(self.path_medoid_weight, (int, float)) \
+                or not 0 <= self.path_medoid_weight < float("inf"):
+            raise ValueError(f"TEST.PATH_MEDOID_WEIGHT must be a finite number >= 0, got {self.path_medoid_weight!r}")
         # PA-MPJPE, V2V and body-scene contact per hypothesis (seeme_amd/mesh_metrics.py): off = today's result, key for key
         self.mesh_metrics = cfg.TEST.get("MESH_METRICS", False)
         if not isinstance(self.mesh_metrics, bool):
@@ -1156,6 +1166,143 @@ class MLD(nn.Module):
             rs["vertices_ref"] = out_ref[1]
             rs["vertices_rst"] = self._feats_to_joints(f_rst0, b_ref, True, orient=o_ref)[1]
         return rs
+
+    # ------------------------------------------------------------------ estimation without labels
+    @torch.no_grad()
+    def predict(self, batch, num_hypotheses=None, betas=None, latents=None, cond_noise=None, step_noise=None):
+        """K hypotheses of the wearer's motion per sequence from the conditions alone.  `batch` has the data module's tuple layout
+        (``split_batch``); the WEARER's slot (index 0) of its motion, transl and beta tensors is never read and may hold anything.
+        Stages 'diffusion' and 'vae_diffusion' only: stage 'vae' reconstructs its target and so needs labels.  The restrictions of
+        ``ego_eval`` hold (no image condition with guidance, K <= 32), and so do its injection points (rows b*K + k, also for K = 1).
+        The prediction is posed with betas [B,10] (zeros when not given) and its OWN global orientation: TEST.GLOBAL_ORIENT_PRED
+        false would need the reference's.
+
+        Returns m_rst_all [B,K,T,F] (renormed), joints_rst_all [B,K,T,24,3], lat_t_all [1,B*K,256], lengths, and hyp_metrics with
+        PAIR_DIST [B,K,K] and medoid_index [B] of ``hyp_pairdist_hip`` -- what can be said about K draws without ground truth."""
+        K = self.num_hypotheses if num_hypotheses is None else self._check_num_hypotheses(num_hypotheses, "num_hypotheses")
+        if self.stage not in ("diffusion", "vae_diffusion"):
+            raise ValueError(f"predict: stage {self.stage!r} reconstructs its target and needs labels; it runs with stage 'diffusion' or "
+                             "'vae_diffusion'")
+        eps_c, eps_u = cond_noise if isinstance(cond_noise, (tuple, list)) else (cond_noise, None)
+        feats_ref, transl, beta, utils_, scene, images, length, _ = split_batch(self.condition, batch)
+        B = feats_ref.shape[0]
+        BK = B * K
+        rep = lambda t: t.repeat_interleave(K, dim=1)                       # [1,B,256] -> [1,B*K,256]
+        scene_tok = img_tok = None
+        if images is not None:
+            if self.do_classifier_free_guidance:
+                raise NotImplementedError("predict with an 'image' condition and guidance_scale > 1 (see ego_eval)")
+            img_tok = rep(self._image_token(images))
+            if scene is not None:
+                scene_tok = rep(self._scene_token(scene))
+        elif scene is not None:
+            scene_tok = rep(self._scene_token(scene))
+            if self.do_classifier_free_guidance:                           # halves in the order of ego_eval (TEST.CFG_SCENE_ORDER)
+                unc = rep(self._scene_token(torch.zeros_like(scene)))
+                scene_tok = torch.cat([scene_tok, unc] if self.cfg_scene_order == "reference" else [unc, scene_tok], dim=1)
+        lengths = length.long().reshape(-1).tolist()
+        dev = feats_ref.device
+
+        def draws(feats, eps):
+            dist = self.vae.encode_dist(feats, lengths)
+            mu, std = rep(dist[0:1]), rep(dist[1:2].exp().pow(0.5))
+            if self.sample_mean:
+                return mu
+            if eps is None:
+                eps = torch.empty_like(mu).normal_()
+            return mu + eps.to(mu).reshape(1, BK, -1) * std
+
+        text_emb = None
+        if "interactee" in self.condition:
+            # the interactee's slot only: _wearer_features(.., 1) slices person 1 out of the motion and the translation
+            # (cut to the longest sequence: the encoder builds its mask from max(lengths) -- a lone last window may be shorter than T)
+            n_enc = min(int(feats_ref.shape[1]), int(max(lengths)))
+            f_int = self._wearer_features(feats_ref[:, :n_enc, 1:2].float(), transl[:, 1:2, :n_enc].float(), 0)
+            text_emb = draws(f_int, eps_c)
+            if self.do_classifier_free_guidance:
+                text_emb = torch.cat([draws(torch.zeros_like(f_int), eps_u), text_emb], dim=1)
+        toks = [t for t in (text_emb, scene_tok, img_tok) if t is not None]
+        if not toks:
+            raise ValueError("no condition tokens")
+        z = self._diffusion_reverse_rows(torch.cat(toks, dim=0).permute(1, 0, 2), BK, latents=latents, step_noise=step_noise)
+        if self.see_future:
+            lengths = [int(i // 2) for i in lengths]
+        min_len = min(feats_ref.shape[1], int(max(lengths)))
+        if betas is None:
+            betas = torch.zeros(B, 10, device=dev, dtype=torch.float32)
+        betas = torch.as_tensor(betas, device=dev, dtype=torch.float32)
+        if tuple(betas.shape) != (B, 10):
+            raise ValueError(f"predict: betas are {tuple(betas.shape)}: expected [B,10] = [{B},10]")
+        b_rst = betas[:, None, :].expand(B, min_len, 10)
+        F = self.vae.nfeats
+        lengths_k = [l for l in lengths for _ in range(K)]
+        f_rst = torch.zeros(BK, min_len, F, device=dev, dtype=torch.float32)
+        joints_all = torch.empty(BK, min_len, 24, 3, device=dev, dtype=torch.float32)
+        for lo, hi in self._row_chunks(BK):                                 # decode, renorm, SMPL joints of <= 512 rows at a time
+            feats_c = self.vae.decode(z[:, lo:hi], lengths_k[lo:hi])        # [n, max length of the chunk, F], zeros past each length
+            tc = min(min_len, feats_c.shape[1])
+            if tc == min_len:
+                fc = feats_c[:, :min_len].contiguous()
+            else:
+                fc = torch.zeros(hi - lo, min_len, F, device=dev, dtype=torch.float32)
+                fc[:, :tc] = feats_c[:, :tc]
+            fc = self.renorm(fc)
+            seq = torch.arange(lo, hi, device=dev) // K
+            f_rst[lo:hi] = fc
+            joints_all[lo:hi] = self._feats_to_joints(fc, b_rst[seq])
+        joints_all = joints_all.view(B, K, min_len, 24, 3)
+        return {"m_rst_all": f_rst.view(B, K, min_len, -1), "joints_rst_all": joints_all, "lat_t_all": z, "lengths": lengths,
+                "hyp_metrics": hyp_pairdist_hip(joints_all, lengths)}
+
+    @torch.no_grad()
+    def predict_recording(self, batch_of_windows, n_frames, overlap=None, betas=None, medoid_weight=None, num_hypotheses=None,
+                          latents=None, cond_noise=None, step_noise=None):
+        """One motion for a recording of `n_frames` frames.  The batch rows are its W windows (``recording.window_plan`` of n_frames,
+        the batch's T and `overlap`; ``recording.windows_batch`` builds them), all in ONE coordinate frame: the seam cost compares
+        global joint positions, so bringing windows of different camera frames into one frame is the caller's job (GIMO scenes
+        are in one frame already).  Steps: ``predict`` (K hypotheses per window) -> ``overlap_cost`` -> unary[w,k] = medoid_weight x
+        sum_j PAIR_DIST[w,k,j] / max(K-1, 1) -> ``path_select`` -> the chosen features -> ``stitch_windows`` -> SMPL joints.
+
+        overlap: None = TEST.WINDOW_OVERLAP, and T // 4 without it.  medoid_weight: None = TEST.PATH_MEDOID_WEIGHT (1.0); 0 passes no
+        unary term, the path then follows the seams alone.  betas [10] or [W,10] pose every window and the stitched motion.
+
+        Returns motion [n_frames,F] (renormed), joints [n_frames,24,3], path [W], seam_cost [W-1] (mm: the disagreement of the two
+        chosen hypotheses on the frames a seam shares), path_cost, window_starts, window_lengths and ``predict``'s result."""
+        from . import recording as R
+        feats_ref, _t, _b, _u, _s, _i, length, _ = split_batch(self.condition, batch_of_windows)
+        W, T = int(feats_ref.shape[0]), int(feats_ref.shape[1])
+        O = overlap if overlap is not None else (self.window_overlap if self.window_overlap is not None else T // 4)
+        if self.see_future:
+            raise NotImplementedError("predict_recording with TEST.SEE_FUTURE: the windows are then half as long as the plan assumes")
+        starts, lens = R.window_plan(n_frames, T, O)
+        if len(starts) != W or length.long().reshape(-1).tolist() != lens:
+            raise ValueError(f"predict_recording: the batch has {W} windows of lengths {length.long().reshape(-1).tolist()}, but the plan "
+                             f"of n_frames {n_frames}, T {T}, overlap {O} is {lens}")
+        mw = self.path_medoid_weight if medoid_weight is None else medoid_weight
+        if isinstance(mw, bool) or not isinstance(mw, (int, float)) or not 0 <= mw < float("inf"):
+            raise ValueError(f"medoid_weight must be a finite number >= 0, got {mw!r}")
+        dev = feats_ref.device
+        if betas is not None:
+            betas = torch.as_tensor(betas, device=dev, dtype=torch.float32)
+            if betas.dim() == 1:
+                betas = betas[None].expand(W, 10)
+        pr = self.predict(batch_of_windows, num_hypotheses=num_hypotheses, betas=betas, latents=latents, cond_noise=cond_noise,
+                          step_noise=step_noise)
+        K = int(pr["m_rst_all"].shape[1])
+        # (a single window shorter than T comes back from predict cut to its length; it has no seam, and the stitch gets it padded)
+        cost = R.overlap_cost_hip(pr["joints_rst_all"], O) if W > 1 else torch.zeros(0, K, K, device=dev, dtype=torch.float32)
+        unary = None
+        if mw > 0:
+            unary = (float(mw) / max(K - 1, 1)) * pr["hyp_metrics"]["PAIR_DIST"].sum(dim=2)
+        sel = R.path_select_hip(cost, unary)
+        chosen = pr["m_rst_all"][torch.arange(W, device=dev), sel["path"]].contiguous()          # [W,T,F]
+        if chosen.shape[1] < T:
+            chosen = torch.nn.functional.pad(chosen, (0, 0, 0, T - chosen.shape[1]))
+        motion = R.stitch_windows_hip(chosen, O, n_frames, R.stitch_layout(self.data_type, self.transl_in_feats))
+        b1 = betas[:1] if betas is not None else torch.zeros(1, 10, device=dev, dtype=torch.float32)
+        joints = self._feats_to_joints(motion[None], b1[:, None, :].expand(1, n_frames, 10))[0]
+        return {"motion": motion, "joints": joints, "path": sel["path"], "seam_cost": sel["seam_cost"], "path_cost": sel["path_cost"],
+                "window_starts": starts, "window_lengths": lens, "predict": pr}
 
     def forward(self, batch, **kw):
         return self.ego_eval(batch, **kw)

@@ -1,0 +1,346 @@
+"""A whole unlabelled recording: windows, one coherent path through their hypotheses, one stitched motion.
+
+The model sees clips of T frames; a recording is cut into W overlapping windows (``window_plan``), every window gets K hypotheses
+(``MLD.predict``), and ONE hypothesis per window is chosen so that neighbouring windows agree on the frames they share:
+
+``overlap_cost_hip``   ``seeme_overlap_cost``: cost [W-1,K,K] (mm), the mean over the O shared frames and the 24 joints of |a - b|,
+                       a = hypothesis i of window w at frame T-O+r, b = hypothesis j of window w+1 at frame r.  No alignment: the
+                       windows are in ONE coordinate frame and the global position is part of what must agree.
+``path_select_hip``    ``seeme_path_select``: the path that minimises sum_w unary[w,p_w] + sum_w cost[w,p_w,p_{w+1}] (dynamic
+                       programming, fp32 sums in window order, the lowest index on a tie), its seam costs and its total.
+``stitch_windows_hip`` ``seeme_stitch_windows``: the chosen windows' renormed features -> one motion [n_frames,F]; on an overlap frame
+                       r takes weight (r+1)/(O+1) for the later window, rotations through unit quaternions (sign-aligned slerp, a
+                       normalised lerp above a dot product of ``NLERP_DOT``), the translation by a plain lerp.
+``*_torch``            their plain-torch twins (any float dtype, any device, any K): the test references, and what serves K > 32.
+
+``load_recording`` / ``windows_batch`` read a recording ``.npz`` and cut it into a batch with the data module's tuple
+layout whose wearer slot is zero.  The definitions are stated once, in include/seeme_hip.h.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import geometry as G
+
+STITCH_ANGLE, STITCH_ANGLE_TRANSL, STITCH_ROT6D = 0, 1, 2
+NLERP_DOT = 0.9995           # SEEME_STITCH_NLERP_DOT
+
+
+# ----------------------------------------------------------------------------- window plan (host)
+def window_plan(n_frames: int, T: int, overlap: int) -> Tuple[List[int], List[int]]:
+    """(starts, lengths) of the windows of a recording: stride S = T - overlap, W = 1 for n_frames <= T, else
+    ceil((n_frames - T) / S) + 1; starts[w] = w*S, lengths[w] = min(T, n_frames - w*S).  2*overlap <= T, so no frame lies in more
+    than two windows; every window but the last is full, the last has at least overlap + 1 frames, and windows w, w+1 share exactly
+    the last `overlap` frames of w and the first `overlap` of w+1."""
+    for name, v in (("n_frames", n_frames), ("T", T), ("overlap", overlap)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"window_plan: {name} must be an integer, got {v!r}")
+    n_frames, T, O = int(n_frames), int(T), int(overlap)
+    if n_frames < 1 or T < 1:
+        raise ValueError(f"window_plan: n_frames and T must be >= 1, got {n_frames}, {T}")
+    if O < 0 or 2 * O > T:
+        raise ValueError(f"window_plan: the overlap must satisfy 0 <= overlap and 2*overlap <= T, got overlap {O}, T {T}")
+    S = T - O
+    W = 1 if n_frames <= T else -(-(n_frames - T) // S) + 1
+    return [w * S for w in range(W)], [min(T, n_frames - w * S) for w in range(W)]
+
+
+def stitch_layout(data_type: str, transl_in_feats: bool) -> int:
+    """The layout argument of ``stitch_windows`` for what ``shapes.motion_layout`` decided."""
+    if data_type == "rot6d":
+        return STITCH_ROT6D
+    return STITCH_ANGLE_TRANSL if transl_in_feats else STITCH_ANGLE
+
+
+# ----------------------------------------------------------------------------- torch twins
+def overlap_cost_torch(jts, overlap: int) -> torch.Tensor:
+    """jts [W,K,T,24,3], any float dtype, any device, any K -> cost [W-1,K,K] (mm); zeros for overlap 0."""
+    W, K, T = jts.shape[:3]
+    O = int(overlap)
+    if O < 0 or 2 * O > T:
+        raise ValueError(f"overlap_cost: the overlap must satisfy 0 <= overlap and 2*overlap <= T, got overlap {O}, T {T}")
+    cost = torch.zeros(max(W - 1, 0), K, K, device=jts.device, dtype=jts.dtype)
+    if W < 2 or O == 0:
+        return cost
+    step = max(1, (1 << 24) // (K * K * O * 72))          # seams per pass: the pair tensor is [step,K,K,O,24,3]
+    for lo in range(0, W - 1, step):
+        hi = min(lo + step, W - 1)
+        a = jts[lo:hi, :, T - O:]                                              # [s,K,O,24,3]
+        b = jts[lo + 1:hi + 1, :, :O]
+        cost[lo:hi] = (a[:, :, None] - b[:, None, :]).norm(dim=-1).sum(dim=(-1, -2)) / 24 / O * 1000.0
+    return cost
+
+
+def _argmin_low(x: torch.Tensor):
+    """min over dim 0 and the LOWEST index that attains it; a NaN among the candidates: (NaN, 0), as the kernel."""
+    n = x.shape[0]
+    best = x.min(dim=0).values                                                 # (torch propagates NaN)
+    ks = torch.arange(n, device=x.device).reshape(n, *([1] * (x.dim() - 1))).expand_as(x)
+    idx = torch.where(x == best, ks, torch.full_like(ks, n)).min(dim=0).values
+    return best, torch.where(idx < n, idx, torch.zeros_like(idx))
+
+
+def path_select_torch(cost, unary=None) -> Dict[str, torch.Tensor]:
+    """cost [W-1,K,K], unary [W,K] or None, any float dtype, any device, any K -> path [W] int64, seam_cost [W-1], path_cost [].
+    d_0 = unary[0] (0 without unary); d_{w+1}[j] = min_i (d_w[i] + cost[w,i,j]) + unary[w+1,j], the lowest i on a tie, the lowest
+    j of the smallest d_{W-1} at the end."""
+    K = int(cost.shape[-1]) if unary is None else int(unary.shape[1])
+    W = int(cost.shape[0]) + 1 if unary is None else int(unary.shape[0])
+    if cost.shape[0] != W - 1 or (W > 1 and tuple(cost.shape[1:]) != (K, K)):
+        raise ValueError(f"path_select: cost is {tuple(cost.shape)} for W = {W}, K = {K}: expected [W-1,K,K]")
+    dev = cost.device
+    d = unary[0].clone() if unary is not None else torch.zeros(K, device=dev, dtype=cost.dtype)
+    back = torch.zeros(max(W - 1, 0), K, dtype=torch.int64, device=dev)
+    for w in range(W - 1):
+        d, back[w] = _argmin_low(d[:, None] + cost[w])
+        if unary is not None:
+            d = d + unary[w + 1]
+    total, last = _argmin_low(d)
+    path = torch.zeros(W, dtype=torch.int64, device=dev)
+    path[W - 1] = last
+    for w in range(W - 2, -1, -1):
+        path[w] = back[w, path[w + 1]]
+    seam = cost[torch.arange(W - 1, device=dev), path[:-1], path[1:]] if W > 1 else cost.new_zeros(0)
+    return {"path": path, "seam_cost": seam, "path_cost": total}
+
+
+def _normalize(q):
+    return q / q.norm(dim=-1, keepdim=True)
+
+
+def _aa_to_quat(a):
+    th = a.norm(dim=-1, keepdim=True)
+    safe = torch.where(th > 1e-6, th, torch.ones_like(th))
+    k = torch.where(th > 1e-6, torch.sin(0.5 * th) / safe, 0.5 - th * th / 48.0)
+    return torch.cat([torch.cos(0.5 * th), k * a], dim=-1)
+
+
+def _rot6d_to_quat(x):
+    """Model-side rot6d (``geometry.rot6d_to_rotmat`` 'prohmr': a1 = x[0:3], a2 = x[3:6], Gram-Schmidt) -> unit quaternion."""
+    a1, a2 = x[..., :3], x[..., 3:6]
+    b1 = a1 / a1.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+    u = a2 - (b1 * a2).sum(-1, keepdim=True) * b1
+    b2 = u / u.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+    return G.rotmat_to_quat_torch(torch.stack([b1, b2, torch.cross(b1, b2, dim=-1)], dim=-1))     # columns b1, b2, b1 x b2
+
+
+def _quat_to_rot6d(q):
+    w, a, b, c = q.unbind(-1)
+    return torch.stack([1.0 - 2.0 * (b * b + c * c), 2.0 * (a * b + w * c), 2.0 * (a * c - w * b),
+                        2.0 * (a * b - w * c), 1.0 - 2.0 * (a * a + c * c), 2.0 * (b * c + w * a)], dim=-1)
+
+
+def _blend(p, q, u):
+    """p, q [...,4] unit quaternions, u [...,1]: q onto p's hemisphere, slerp (normalised lerp above NLERP_DOT), normalised."""
+    dt = (p * q).sum(-1, keepdim=True)
+    q = torch.where(dt < 0, -q, q)
+    dt = dt.abs()
+    near = dt > NLERP_DOT
+    th = torch.acos(torch.where(near, torch.zeros_like(dt), dt))
+    s = torch.sin(th)
+    kp = torch.where(near, 1.0 - u, torch.sin((1.0 - u) * th) / s)
+    kq = torch.where(near, u, torch.sin(u * th) / s)
+    return _normalize(kp * p + kq * q)
+
+
+def _check_stitch(W, T, O, n_frames, F, layout):
+    starts, _ = window_plan(n_frames, T, O)
+    if len(starts) != W:
+        raise ValueError(f"stitch_windows: {W} windows, but the plan of n_frames {n_frames}, T {T}, overlap {O} has {len(starts)}")
+    if layout == STITCH_ROT6D:
+        ok = F == 144
+    elif layout in (STITCH_ANGLE, STITCH_ANGLE_TRANSL):
+        ok = F >= 3 and F % 3 == 0 and (layout == STITCH_ANGLE or F >= 6)
+    else:
+        raise ValueError(f"stitch_windows: unknown layout {layout!r}")
+    if not ok:
+        raise ValueError(f"stitch_windows: features are {F} wide: expected J x 3 (+ 3 translation values) or 24 x 6 for rot6d")
+
+
+def stitch_windows_torch(feats, overlap: int, n_frames: int, layout: int) -> torch.Tensor:
+    """feats [W,T,F] renormed features of the chosen hypotheses, any float dtype, any device -> [n_frames,F]."""
+    W, T, F = feats.shape
+    O = int(overlap)
+    _check_stitch(W, T, O, n_frames, F, layout)
+    dev = feats.device
+    S = T - O
+    n = torch.arange(n_frames, device=dev)
+    w = (n // S).clamp(max=W - 1)
+    t = n - w * S
+    out = feats[w, t].clone()
+    ov = ((w >= 1) & (t < O)).nonzero()[:, 0]
+    if ov.numel() == 0:
+        return out
+    wo, to = w[ov], t[ov]
+    a, b = feats[wo - 1, to + S], feats[wo, to]                                # earlier, later: [n_ov,F]
+    u = ((to + 1).to(feats.dtype) / (O + 1))[:, None, None]
+    if layout == STITCH_ROT6D:
+        y = _quat_to_rot6d(_blend(_rot6d_to_quat(a.reshape(-1, 24, 6)), _rot6d_to_quat(b.reshape(-1, 24, 6)), u)).reshape(-1, F)
+    else:
+        nr = F - 3 if layout == STITCH_ANGLE_TRANSL else F
+        y = G.quat_to_aa_torch(_blend(_aa_to_quat(a[:, :nr].reshape(len(ov), -1, 3)), _aa_to_quat(b[:, :nr].reshape(len(ov), -1, 3)), u))
+        y = y.reshape(len(ov), nr)
+        if layout == STITCH_ANGLE_TRANSL:
+            y = torch.cat([y, a[:, nr:] + u[:, 0] * (b[:, nr:] - a[:, nr:])], dim=1)
+    out[ov] = y
+    return out
+
+
+# ----------------------------------------------------------------------------- kernels
+_WS: Dict[tuple, torch.Tensor] = {}
+
+
+def _workspace(dev, need: int) -> torch.Tensor:
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)             # per stream: launches of one stream run in order
+    ws = _WS.get(key)
+    if ws is None or ws.numel() < max(need, 16):
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        _WS[key] = ws
+    return ws
+
+
+def overlap_cost_hip(jts, overlap: int) -> torch.Tensor:
+    """jts [W,K,T,24,3] fp32 on the device, K <= 32 (``overlap_cost_torch`` serves K > 32) -> cost [W-1,K,K] (mm)."""
+    L.require_cuda(jts, "jts")
+    if jts.dim() != 5 or tuple(jts.shape[3:]) != (24, 3):
+        raise L.SeemeError(f"overlap_cost: joints are {tuple(jts.shape)}: expected [W,K,T,24,3]")
+    W, K, T = (int(n) for n in jts.shape[:3])
+    return _launch_overlap(jts.contiguous(), W, K, T, int(overlap))
+
+
+def _launch_overlap(jts, W, K, T, O, ws_bytes=None) -> torch.Tensor:
+    lib = L.lib()
+    need = int(lib.seeme_overlap_cost_workspace_bytes(W, K, T, O))
+    ws = _workspace(jts.device, need)
+    # (the kernel writes nothing for O = 0: the cost of sharing no frame is 0)
+    cost = (torch.zeros if O == 0 else torch.empty)(max(W - 1, 0), max(K, 0), max(K, 0), device=jts.device, dtype=torch.float32)
+    L.check(lib.seeme_overlap_cost(jts.data_ptr(), W, K, T, O, cost.data_ptr(), ws.data_ptr(), need if ws_bytes is None else ws_bytes,
+                                   L.current_stream()), "seeme_overlap_cost")
+    return cost
+
+
+def path_select_hip(cost, unary=None) -> Dict[str, torch.Tensor]:
+    """cost [W-1,K,K], unary [W,K] or None, fp32 on the device, K <= 32 -> path [W] int64, seam_cost [W-1], path_cost []."""
+    L.require_cuda(cost, "cost")
+    if unary is not None:
+        L.require_cuda(unary, "unary")
+    K = int(cost.shape[-1]) if unary is None else int(unary.shape[1])
+    W = int(cost.shape[0]) + 1 if unary is None else int(unary.shape[0])
+    if cost.dim() != 3 or cost.shape[0] != W - 1 or (W > 1 and tuple(cost.shape[1:]) != (K, K)):
+        raise L.SeemeError(f"path_select: cost is {tuple(cost.shape)} for W = {W}, K = {K}: expected [W-1,K,K]")
+    return _launch_path(cost.contiguous(), None if unary is None else unary.contiguous(), W, K)
+
+
+def _launch_path(cost, unary, W, K, ws_bytes=None) -> Dict[str, torch.Tensor]:
+    dev = cost.device
+    lib = L.lib()
+    need = int(lib.seeme_path_select_workspace_bytes(W, K))
+    ws = _workspace(dev, need)
+    path = torch.empty(max(W, 0), device=dev, dtype=torch.int32)
+    seam = torch.empty(max(W - 1, 0), device=dev, dtype=torch.float32)
+    total = torch.empty(1, device=dev, dtype=torch.float32)
+    L.check(lib.seeme_path_select(cost.data_ptr(), L.ptr(unary), W, K, path.data_ptr(), seam.data_ptr(), total.data_ptr(), ws.data_ptr(),
+                                  need if ws_bytes is None else ws_bytes, L.current_stream()), "seeme_path_select")
+    return {"path": path.long(), "seam_cost": seam, "path_cost": total[0]}
+
+
+def stitch_windows_hip(feats, overlap: int, n_frames: int, layout: int) -> torch.Tensor:
+    """feats [W,T,F] renormed features of the chosen hypotheses, fp32 on the device -> [n_frames,F]."""
+    L.require_cuda(feats, "feats")
+    if feats.dim() != 3:
+        raise L.SeemeError(f"stitch_windows: features are {tuple(feats.shape)}: expected [W,T,F]")
+    W, T, F = (int(n) for n in feats.shape)
+    out = torch.empty(max(int(n_frames), 0), F, device=feats.device, dtype=torch.float32)
+    L.check(L.lib().seeme_stitch_windows(feats.contiguous().data_ptr(), W, T, int(overlap), int(n_frames), F, int(layout), out.data_ptr(),
+                                         L.current_stream()), "seeme_stitch_windows")
+    return out
+
+
+# ----------------------------------------------------------------------------- recording files
+_REC_KEYS = ("global_orient", "body_pose", "transl", "betas")
+
+
+def load_recording(path: str) -> Dict[str, np.ndarray]:
+    """A recording ``.npz`` (read with allow_pickle=False: an object array is refused): the INTERACTEE's global_orient [L,3],
+    body_pose [L,69|63], transl [L,3], betas [10]; optionally scene [P,3], image_feats [L,2048], wearer_betas [10].  float32."""
+    with np.load(path, allow_pickle=False) as z:
+        missing = [k for k in _REC_KEYS if k not in z.files]
+        if missing:
+            raise ValueError(f"{path}: missing {missing}; a recording holds {list(_REC_KEYS)} of the interactee")
+        rec = {k: np.asarray(z[k], np.float32) for k in _REC_KEYS + ("scene", "image_feats", "wearer_betas") if k in z.files}
+    n = rec["global_orient"].shape[0]
+    want = {"global_orient": [(n, 3)], "body_pose": [(n, 69), (n, 63)], "transl": [(n, 3)], "betas": [(10,)], "wearer_betas": [(10,)],
+            "image_feats": [(n, 2048)]}
+    if n < 1:
+        raise ValueError(f"{path}: the recording has no frame")
+    for k, shapes in want.items():
+        if k in rec and rec[k].shape not in shapes:
+            raise ValueError(f"{path}: {k} is {rec[k].shape}: expected {' or '.join(str(list(s)) for s in shapes)} (L = {n})")
+    if "scene" in rec and (rec["scene"].ndim != 2 or rec["scene"].shape[1] != 3 or rec["scene"].shape[0] < 1):
+        raise ValueError(f"{path}: scene is {rec['scene'].shape}: expected [P,3]")
+    rec["n_frames"] = n
+    return rec
+
+
+def _stats_of(dm_or_stats):
+    """(mean [1,D], std [1,D]) as numpy, and the data module's own dataset name / data type when it states them."""
+    if isinstance(dm_or_stats, (tuple, list)):
+        mean, std = dm_or_stats
+        return np.asarray(mean, np.float32).reshape(1, -1), np.asarray(std, np.float32).reshape(1, -1), None, None
+    dm = dm_or_stats
+    mean, std = (torch.as_tensor(x).detach().float().cpu().numpy().reshape(1, -1) for x in (dm.mean, dm.std))
+    if not hasattr(dm, "splits"):            # the synthetic module renorms with the first nfeats statistics
+        mean, std = mean[:, :dm.nfeats], std[:, :dm.nfeats]
+    return mean, std, getattr(dm, "name", None), getattr(dm, "data_type", None)
+
+
+def windows_batch(rec, datamodule_or_stats, T: int, overlap: int, condition, dataset: Optional[str] = None,
+                  data_type: Optional[str] = None, predict_transl: bool = True, device=None):
+    """The W windows of a recording as ONE batch with the data module's tuple layout (``mld.split_batch``): motion [W,T,2,D], transl
+    [W,2,T,3], beta [W,2,T,10], utils [W,T,6], [scene [W,P,3]], [images [W,2048]], length [W,1].  The interactee (slot 1) is
+    normalised by the rule the data module applies at load time (``data.normalise_person`` / ``data.normalise_rot6d``: zero padding to
+    T first); the wearer's slot (0) is all zeros.  A window's image features are those of its centre frame.  Returns (batch, starts,
+    lengths).  datamodule_or_stats: a data module (``mean`` / ``std``) or the pair (mean, std)."""
+    from .data import load_time_stats, normalise_person, normalise_rot6d
+    mean, std, dm_name, dm_type = _stats_of(datamodule_or_stats)
+    n = int(rec["n_frames"])
+    P = rec["body_pose"].shape[1]
+    dataset = dataset or dm_name or ("egobody" if P == 69 else "gimo")
+    data_type = data_type or dm_type or "angle"
+    if P != (69 if dataset == "egobody" else 63):
+        raise ValueError(f"windows_batch: body_pose is {P} wide, dataset '{dataset}' poses {69 if dataset == 'egobody' else 63} values")
+    rot6d = data_type == "rot6d"
+    starts, lengths = window_plan(n, T, overlap)
+    W = len(starts)
+    m, s = load_time_stats(mean, std, rot6d)
+    motion = np.zeros((W, T, 2, 3 + P), np.float32)
+    transl = np.zeros((W, 2, T, 3), np.float32)
+    beta = np.zeros((W, 2, T, 10), np.float32)
+    for w, (lo, ln) in enumerate(zip(starts, lengths)):
+        go, bp, tr = np.zeros((T, 3), np.float32), np.zeros((T, P), np.float32), np.zeros((T, 3), np.float32)
+        go[:ln], bp[:ln], tr[:ln] = rec["global_orient"][lo:lo + ln], rec["body_pose"][lo:lo + ln], rec["transl"][lo:lo + ln]
+        motion[w, :, 1], transl[w, 1] = normalise_person(go, bp, tr, m, s, dataset, bool(predict_transl) and not rot6d)
+        beta[w, 1, :ln] = rec["betas"]
+    length = torch.tensor(lengths, dtype=torch.long).reshape(W, 1)
+    motion_t = torch.from_numpy(motion)
+    if rot6d:
+        motion_t = normalise_rot6d(motion_t, length, mean, std)
+        motion_t[:, :, 0] = 0.0                                                # the wearer's slot stays zero
+    out = [motion_t, torch.from_numpy(transl), torch.from_numpy(beta), torch.zeros(W, T, 6)]
+    if "scene" in condition:
+        if "scene" not in rec:
+            raise ValueError("windows_batch: the model has a 'scene' condition and the recording holds no scene cloud")
+        out.append(torch.from_numpy(rec["scene"])[None].expand(W, -1, -1).contiguous())
+    if "image" in condition:
+        if "image_feats" not in rec:
+            raise ValueError("windows_batch: the model has an 'image' condition and the recording holds no image_feats")
+        centre = [lo + ln // 2 for lo, ln in zip(starts, lengths)]
+        out.append(torch.from_numpy(rec["image_feats"][centre]).contiguous())
+    out.append(length)
+    if device is not None:
+        out = [t.to(device) for t in out]
+    return tuple(out), starts, lengths
