@@ -629,6 +629,28 @@ enum { SEEME_STITCH_ANGLE = 0, SEEME_STITCH_ANGLE_TRANSL = 1, SEEME_STITCH_ROT6D
 #define SEEME_STITCH_NLERP_DOT 0.9995f
 int seeme_stitch_windows(const float* feats, int W, int T, int O, int n_frames, int F, int layout, float* out, void* stream);
 
+/* ------------------------------------------------------------------ scene views of a moving camera (csrc/scene_views.hip)
+ * The view-dependent selection of a scene mesh's vertices that the EgoBody scene tables are made with (EgoHMR
+ * preprocess_scene_s1.py:91-114: into the camera frame, keep z > 0, every k-th survivor, the first P), for W views in one call.
+ * verts [N,3] fp32; M [W,4,4] fp32 row-major, world -> view, rows 0..2 are read; cloud [W,P,3] fp32 in the view's frame; index
+ * [W,P] int32, the source vertex of every output row; count [W] int32, the number of survivors.
+ * For vertex i = (x, y, z) and view w, coordinate c of the moved vertex is
+ *     p'_c = fmaf(M[c][2], z, fmaf(M[c][1], y, fmaf(M[c][0], x, M[c][3])))
+ * and the vertex survives iff p'_z > 0 (a NaN compares false); the classification and the written coordinate are this one
+ * expression.  Survivors keep vertex order; r is a survivor's rank among its view's survivors.
+ *   count >= P:      k = count / P (integer division, >= 1); output row j < P holds the survivor of rank j*k.
+ *   0 < count < P:   row j holds the survivor of rank j mod count (the table is filled cyclically; count tells the caller).
+ *   count = 0:       the rows are zero and index is -1; no error.
+ * 1 <= N <= 2^24, 1 <= W <= 4096, 1 <= P <= 2^20.  A workgroup owns a tile of SEEME_SCENE_VIEW_TILE consecutive vertices and walks
+ * SEEME_SCENE_VIEW_WINDOWS_PER_PASS views over it.  No atomics; a row's owner is found from ranks alone, so the output is bitwise
+ * reproducible and does not depend on W, on the tiling or on what the workspace held.  The workspace (4-byte aligned) holds the
+ * survivor count of every (view, tile), then its exclusive prefix. */
+#define SEEME_SCENE_VIEW_TILE 1024
+#define SEEME_SCENE_VIEW_WINDOWS_PER_PASS 16
+size_t seeme_scene_views_workspace_bytes(int N, int W, int P);           /* 0 for bad sizes */
+int seeme_scene_views(const float* verts, const float* M, int N, int W, int P, float* cloud, int32_t* index, int32_t* count,
+                      void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ per-frame mesh metrics (csrc/mesh_metrics.hip)
  * Frame-level primitives of the EgoHMR tables (test_egohmr.py:463-492, 540-549): one float per frame, fp32 metres in and out, a
  * frame whose map entry is negative is skipped and gets 0; the caller averages over the valid frames of a sequence and chunks the

@@ -470,8 +470,12 @@ def predict_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=N
     g.add_argument("--seed", type=int, default=None, help="seed of the draws (default: SEED_VALUE)")
     g.add_argument("--save_hypotheses", action="store_true", help="also store m_rst_all [W,K,T,F], every window's K hypotheses")
     p.set_defaults(frames=None)                                         # the window length: MOTION_LENGTH unless --frames says otherwise
+    p.set_defaults(scene_points=None)                                   # rows of a scene view: TEST.SCENE_VIEW_POINTS unless given
     args = p.parse_args(argv)
     cfg = load_cfg(args, "test")
+    if args.scene_points is not None:
+        cfg.TEST.SCENE_VIEW_POINTS = args.scene_points
+    args.scene_points = int(cfg.TEST.get("SCENE_VIEW_POINTS", 20000))
     args.frames = T = int(args.frames or cfg.MOTION_LENGTH)
     log = make_logger(cfg, "predict", 0)
     if not torch.cuda.is_available():
@@ -491,16 +495,29 @@ def predict_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=N
     model = model.to(dev).eval()
     rec = R.load_recording(args.input)
     O = model.window_overlap if model.window_overlap is not None else T // 4
-    batch, starts, lengths = R.windows_batch(rec, dm, T, O, tuple(cfg.model.condition), dataset=str(cfg.DATASET_NAME),
-                                             data_type=str(cfg.DATA_TYPE), predict_transl=bool(cfg.TRAIN.ABLATION.PREDICT_TRANSL),
-                                             device=dev)
+    moving = "world2cam" in rec                                         # every window in the camera frame of its first frame
+    pelvis = R.rest_pelvis(model.smpl_model, torch.from_numpy(rec["betas"]).to(dev)[None])[0] if moving else None
+    made = R.windows_batch(rec, dm, T, O, tuple(cfg.model.condition), dataset=str(cfg.DATASET_NAME), data_type=str(cfg.DATA_TYPE),
+                           predict_transl=bool(cfg.TRAIN.ABLATION.PREDICT_TRANSL), device=dev, scene_points=model.scene_view_points,
+                           pelvis=pelvis)
+    batch, starts, lengths = made[:3]
+    frames = made[3] if moving else None
     torch.manual_seed(int(cfg.SEED_VALUE) if args.seed is None else args.seed)
     betas = torch.from_numpy(rec["wearer_betas"]).to(dev) if "wearer_betas" in rec else None
-    out = model.predict_recording(batch, rec["n_frames"], overlap=O, betas=betas)
+    out = model.predict_recording(batch, rec["n_frames"], overlap=O, betas=betas,
+                                  window_frames=frames["world2cam"].float() if moving else None)
     nb = 69 if model.name_dataset == "egobody" else 63
     res = {k: v.float().cpu().numpy() for k, v in motion_to_smpl(out["motion"], model.data_type, model.transl_in_feats, nb).items()}
     res.update(joints=out["joints"].cpu().numpy(), window_starts=np.asarray(starts, np.int64), path=out["path"].cpu().numpy(),
                seam_cost=out["seam_cost"].cpu().numpy())
+    if moving:                                                          # everything above is in the recording's world frame
+        res["world2cam_windows"] = frames["world2cam"].numpy()
+        if frames["scene_view_count"] is not None:
+            res["scene_view_count"] = frames["scene_view_count"].cpu().numpy()
+            empty = np.flatnonzero(res["scene_view_count"] == 0)
+            if empty.size:
+                raise ValueError(f"{args.input}: window {int(empty[0])} (frames {starts[empty[0]]}..{starts[empty[0]] + lengths[empty[0]] - 1}) "
+                                 "sees no scene vertex (scene_view_count 0): its camera pose looks away from scene_vertices")
     if args.save_hypotheses:
         res["m_rst_all"] = out["predict"]["m_rst_all"].cpu().numpy()
     d = os.path.dirname(os.path.abspath(args.output))

@@ -374,6 +374,11 @@ class MLD(nn.Module):
         if self.window_overlap is not None and (isinstance(self.window_overlap, bool) or not isinstance(self.window_overlap, int)
                                                 or self.window_overlap < 0):
             raise ValueError(f"TEST.WINDOW_OVERLAP must be an integer >= 0 (at most half the window), got {self.window_overlap!r}")
+        # rows of a window's scene view when a recording brings the scene's vertices and a camera pose per frame (recording.py)
+        self.scene_view_points = cfg.TEST.get("SCENE_VIEW_POINTS", 20000)
+        if isinstance(self.scene_view_points, bool) or not isinstance(self.scene_view_points, int) \
+                or not 1 <= self.scene_view_points <= 1 << 20:
+            raise ValueError(f"TEST.SCENE_VIEW_POINTS must be an integer in 1..2^20, got {self.scene_view_points!r}")
         self.path_medoid_weight = cfg.TEST.get("PATH_MEDOID_WEIGHT", 1.0)
         if isinstance(self.path_medoid_weight, bool) or not isinstance(self.path_medoid_weight, (int, float)) \
                 or not 0 <= self.path_medoid_weight < float("inf"):
@@ -1256,18 +1261,24 @@ class MLD(nn.Module):
 
     @torch.no_grad()
     def predict_recording(self, batch_of_windows, n_frames, overlap=None, betas=None, medoid_weight=None, num_hypotheses=None,
-                          latents=None, cond_noise=None, step_noise=None):
+                          latents=None, cond_noise=None, step_noise=None, window_frames=None):
         """One motion for a recording of `n_frames` frames.  The batch rows are its W windows (``recording.window_plan`` of n_frames,
-        the batch's T and `overlap`; ``recording.windows_batch`` builds them), all in ONE coordinate frame: the seam cost compares
-        global joint positions, so bringing windows of different camera frames into one frame is the caller's job (GIMO scenes
-        are in one frame already).  Steps: ``predict`` (K hypotheses per window) -> ``overlap_cost`` -> unary[w,k] = medoid_weight x
+        the batch's T and `overlap`; ``recording.windows_batch`` builds them), all in ONE coordinate frame unless `window_frames` says
+        otherwise: the seam cost compares global joint positions (GIMO scenes are in one frame already; a moving camera: below).  Steps: ``predict`` (K hypotheses per window) -> ``overlap_cost`` -> unary[w,k] = medoid_weight x
         sum_j PAIR_DIST[w,k,j] / max(K-1, 1) -> ``path_select`` -> the chosen features -> ``stitch_windows`` -> SMPL joints.
 
         overlap: None = TEST.WINDOW_OVERLAP, and T // 4 without it.  medoid_weight: None = TEST.PATH_MEDOID_WEIGHT (1.0); 0 passes no
         unary term, the path then follows the seams alone.  betas [10] or [W,10] pose every window and the stitched motion.
 
         Returns motion [n_frames,F] (renormed), joints [n_frames,24,3], path [W], seam_cost [W-1] (mm: the disagreement of the two
-        chosen hypotheses on the frames a seam shares), path_cost, window_starts, window_lengths and ``predict``'s result."""
+        chosen hypotheses on the frames a seam shares), path_cost, window_starts, window_lengths and ``predict``'s result.
+
+        window_frames [W,4,4]: every window is in a frame of its OWN, M_w mapping the common (world) frame to window w's
+        (``recording.windows_batch`` with world2cam).  The hypotheses' joints are then brought to the world frame by the inverse of
+        M_w before the seams are compared, the chosen windows' features are re-framed the same way (the orientation, and the
+        translation when the features carry it: ``recording.reframe_smpl`` / ``reframe_rot6d``) before they are stitched, and motion,
+        joints and seam_cost are in the world frame; ``predict``'s result stays in the windows' frames and the result gains
+        window_frames.  The medoid term is invariant under a rigid map and is taken as it is."""
         from . import recording as R
         feats_ref, _t, _b, _u, _s, _i, length, _ = split_batch(self.condition, batch_of_windows)
         W, T = int(feats_ref.shape[0]), int(feats_ref.shape[1])
@@ -1289,20 +1300,41 @@ class MLD(nn.Module):
         pr = self.predict(batch_of_windows, num_hypotheses=num_hypotheses, betas=betas, latents=latents, cond_noise=cond_noise,
                           step_noise=step_noise)
         K = int(pr["m_rst_all"].shape[1])
+        jts = pr["joints_rst_all"]
+        if window_frames is not None:
+            Mw = torch.as_tensor(window_frames, device=dev)
+            if tuple(Mw.shape) != (W, 4, 4):
+                raise ValueError(f"predict_recording: window_frames are {tuple(Mw.shape)}: expected [W,4,4] = [{W},4,4]")
+            Ai, ai = R.rigid_parts(R.rigid_inverse(Mw.double()).float())            # window frame -> world
+            b0 = torch.zeros(W, 10, device=dev, dtype=torch.float32)               # (rot6d is posed with zero betas)
+            J0 = R.rest_pelvis(self.smpl_model, b0 if betas is None or self.data_type == "rot6d" else betas)
+            jts = R.reframe_joints(jts, J0[:, None, None], Ai[:, None, None], ai[:, None, None], self.transl_in_feats).contiguous()
         # (a single window shorter than T comes back from predict cut to its length; it has no seam, and the stitch gets it padded)
-        cost = R.overlap_cost_hip(pr["joints_rst_all"], O) if W > 1 else torch.zeros(0, K, K, device=dev, dtype=torch.float32)
+        cost = R.overlap_cost_hip(jts, O) if W > 1 else torch.zeros(0, K, K, device=dev, dtype=torch.float32)
         unary = None
         if mw > 0:
             unary = (float(mw) / max(K - 1, 1)) * pr["hyp_metrics"]["PAIR_DIST"].sum(dim=2)
         sel = R.path_select_hip(cost, unary)
         chosen = pr["m_rst_all"][torch.arange(W, device=dev), sel["path"]].contiguous()          # [W,T,F]
+        if window_frames is not None:
+            if self.data_type == "rot6d":
+                chosen[..., :6] = R.reframe_rot6d(chosen[..., :6], Ai[:, None])
+            else:
+                tr = chosen[..., -3:] if self.transl_in_feats else torch.zeros_like(chosen[..., :3])
+                go_w, tr_w = R.reframe_smpl(chosen[..., :3], tr, J0[:, None], Ai[:, None], ai[:, None])
+                chosen[..., :3] = go_w
+                if self.transl_in_feats:
+                    chosen[..., -3:] = tr_w
         if chosen.shape[1] < T:
             chosen = torch.nn.functional.pad(chosen, (0, 0, 0, T - chosen.shape[1]))
         motion = R.stitch_windows_hip(chosen, O, n_frames, R.stitch_layout(self.data_type, self.transl_in_feats))
         b1 = betas[:1] if betas is not None else torch.zeros(1, 10, device=dev, dtype=torch.float32)
         joints = self._feats_to_joints(motion[None], b1[:, None, :].expand(1, n_frames, 10))[0]
-        return {"motion": motion, "joints": joints, "path": sel["path"], "seam_cost": sel["seam_cost"], "path_cost": sel["path_cost"],
-                "window_starts": starts, "window_lengths": lens, "predict": pr}
+        out = {"motion": motion, "joints": joints, "path": sel["path"], "seam_cost": sel["seam_cost"], "path_cost": sel["path_cost"],
+               "window_starts": starts, "window_lengths": lens, "predict": pr}
+        if window_frames is not None:
+            out["window_frames"] = Mw
+        return out
 
     def forward(self, batch, **kw):
         return self.ego_eval(batch, **kw)

@@ -13,6 +13,10 @@ The model sees clips of T frames; a recording is cut into W overlapping windows 
                        normalised lerp above a dot product of ``NLERP_DOT``), the translation by a plain lerp.
 ``*_torch``            their plain-torch twins (any float dtype, any device, any K): the test references, and what serves K > 32.
 
+``scene_views_hip``    ``seeme_scene_views``: the view-dependent selection of a scene mesh's vertices (into the view's frame, z > 0, every
+                       k-th survivor, the first P) for W camera poses in one call; ``scene_views_torch`` is its twin.
+``reframe_smpl`` / ``reframe_rot6d`` / ``reframe_joints``: a rigid map p -> A p + a applied to SMPL parameters and to joints, plain torch.
+
 ``load_recording`` / ``windows_batch`` read a recording ``.npz`` and cut it into a batch with the data module's tuple
 layout whose wearer slot is zero.  The definitions are stated once, in include/seeme_hip.h.
 """
@@ -28,6 +32,9 @@ from . import geometry as G
 
 STITCH_ANGLE, STITCH_ANGLE_TRANSL, STITCH_ROT6D = 0, 1, 2
 NLERP_DOT = 0.9995           # SEEME_STITCH_NLERP_DOT
+SCENE_VIEW_TILE = 1024               # SEEME_SCENE_VIEW_TILE: vertices of one workgroup of seeme_scene_views
+SCENE_VIEW_WINDOWS_PER_PASS = 16     # SEEME_SCENE_VIEW_WINDOWS_PER_PASS: views a workgroup walks over its tile
+SCENE_VIEW_POINTS = 20000            # rows of an EgoBody scene table (TEST.SCENE_VIEW_POINTS)
 
 
 # ----------------------------------------------------------------------------- window plan (host)
@@ -190,6 +197,118 @@ def stitch_windows_torch(feats, overlap: int, n_frames: int, layout: int) -> tor
     return out
 
 
+# ----------------------------------------------------------------------------- scene views: the twin
+def _view_coord(M, c: int, x, y, z):
+    """Coordinate c of the moved vertices, in the order of the kernel's fmaf chain (torch has no fused multiply-add: two roundings
+    per step where the kernel has one).  M [w,4,4]; x, y, z [N] or [w,P] -> [w,N] or [w,P]."""
+    return M[:, c, 2, None] * z + (M[:, c, 1, None] * y + (M[:, c, 0, None] * x + M[:, c, 3, None]))
+
+
+def scene_views_torch(verts, world2view, P: int) -> Dict[str, torch.Tensor]:
+    """verts [N,3], world2view [W,4,4] (rows 0..2 are read), any float dtype, any device -> cloud [W,P,3] in the view's frame, index
+    [W,P] int32 (the source vertex of every row), count [W] int32: the definition of ``seeme_scene_views`` (include/seeme_hip.h).  No
+    host synchronisation: the row of rank r is found by a search in the running survivor count.  In fp32 its ``z > 0`` may differ
+    from the kernel's for vertices within rounding of the view's plane (the kernel fuses every multiply-add); in float64 on inputs
+    that keep a margin from the plane it is the kernel's reference."""
+    if verts.dim() != 2 or verts.shape[1] != 3 or world2view.dim() != 3 or tuple(world2view.shape[1:]) != (4, 4):
+        raise ValueError(f"scene_views: verts are {tuple(verts.shape)}, world2view is {tuple(world2view.shape)}: expected [N,3] and [W,4,4]")
+    N, W, P = int(verts.shape[0]), int(world2view.shape[0]), int(P)
+    if N < 1 or W < 1 or P < 1:
+        raise ValueError(f"scene_views: N, W and P must be >= 1, got {N}, {W}, {P}")
+    dev = verts.device
+    M = world2view.to(verts.dtype)
+    x, y, z = verts.unbind(-1)
+    j = torch.arange(P, device=dev)
+    cloud = torch.zeros(W, P, 3, device=dev, dtype=verts.dtype)
+    index = torch.full((W, P), -1, device=dev, dtype=torch.int32)
+    count = torch.zeros(W, device=dev, dtype=torch.int32)
+    step = max(1, (1 << 24) // N)                                              # views per pass: the temporaries are [step,N]
+    for lo in range(0, W, step):
+        Mc = M[lo:lo + step]
+        running = (_view_coord(Mc, 2, x, y, z) > 0).cumsum(dim=1)              # [w,N] survivors up to and including vertex i
+        n = running[:, -1]
+        k = torch.div(n, P, rounding_mode="floor").clamp(min=1)
+        rank = torch.where((n >= P)[:, None], j[None] * k[:, None], j[None] % n.clamp(min=1)[:, None])
+        at = torch.searchsorted(running, rank + 1).clamp(max=N - 1)            # the first vertex whose running count reaches rank + 1
+        px, py, pz = verts[at].unbind(-1)                                      # [w,P]
+        rows = torch.stack([_view_coord(Mc, c, px, py, pz) for c in range(3)], dim=-1)
+        some = (n > 0)[:, None]
+        cloud[lo:lo + step] = torch.where(some[..., None], rows, torch.zeros_like(rows))
+        index[lo:lo + step] = torch.where(some, at, torch.full_like(at, -1)).to(torch.int32)
+        count[lo:lo + step] = n.to(torch.int32)
+    return {"cloud": cloud, "index": index, "count": count}
+
+
+# ----------------------------------------------------------------------------- rigid re-framing of SMPL parameters and joints
+def _apply(A, v):
+    """A [...,3,3] on v [...,3] (leading dimensions broadcast)."""
+    return (A @ v[..., None])[..., 0]
+
+
+def _quat_mul(p, q):
+    pw, px, py, pz = p.unbind(-1)
+    qw, qx, qy, qz = q.unbind(-1)
+    return torch.stack([pw * qw - px * qx - py * qy - pz * qz, pw * qx + px * qw + py * qz - pz * qy,
+                        pw * qy - px * qz + py * qw + pz * qx, pw * qz + px * qy - py * qx + pz * qw], dim=-1)
+
+
+def rigid_parts(M):
+    """[...,4,4] -> (A [...,3,3], a [...,3]) of p -> A p + a."""
+    return M[..., :3, :3], M[..., :3, 3]
+
+
+def rigid_inverse(M):
+    """[...,4,4] rigid maps -> their inverses (A^T, -A^T a)."""
+    A, a = rigid_parts(M)
+    At = A.transpose(-1, -2)
+    out = torch.zeros_like(M)
+    out[..., :3, :3], out[..., :3, 3], out[..., 3, 3] = At, -_apply(At, a), 1.0
+    return out
+
+
+def rest_pelvis(smpl_model, betas):
+    """J0 [n,3]: joint 0 of the SMPL layer at zero pose and zero translation for betas [n,10] (in their dtype, on their device).  The
+    regressor is folded into the template and the shape directions in the model's own dtype, as the SMPL kernels and their twins
+    fold it, so J0 is the pelvis they rotate about."""
+    b = betas.reshape(-1, 10)
+    J_t = (smpl_model.J_regressor @ smpl_model.v_template)[0].to(b)                                   # [3]
+    J_s = torch.einsum("jv,vkl->jkl", smpl_model.J_regressor, smpl_model.shapedirs)[0].to(b)          # [3,10]
+    return J_t[None] + b @ J_s.T
+
+
+def reframe_smpl(global_orient, transl, J0, A, a):
+    """SMPL parameters of the same body seen through p -> A p + a: go' = log(A exp(go)), t' = A (J0 + t) + a - J0 (SMPL rotates about
+    the rest pelvis J0: joints = R_g (X - J0) + J0 + t).  global_orient, transl [...,3]; J0, a [...,3] and A [...,3,3] broadcast
+    over the leading dimensions.  Plain torch, any float dtype, any device; go' has an angle in [0, pi]."""
+    q = _quat_mul(G.rotmat_to_quat_torch(A.to(global_orient)), _aa_to_quat(global_orient))
+    J0, a = J0.to(transl), a.to(transl)
+    return G.quat_to_aa_torch(_normalize(q)), _apply(A.to(transl), J0 + transl) + a - J0
+
+
+def reframe_rot6d(x6, A):
+    """The 6-D variant for model-side rot6d features (``geometry.rot6d_to_rotmat`` 'prohmr': x[0:3], x[3:6] -> columns b1, b2):
+    x6 [...,6] -> the first two columns of A R.  fp32 on the device goes through the kernel, anything else through its torch twin."""
+    if x6.is_cuda and x6.dtype == torch.float32:
+        R = G.rot6d_to_rotmat(x6.reshape(-1, 6).contiguous())
+    else:
+        from .vae_autograd import rot6d_to_rotmat_torch
+        R = rot6d_to_rotmat_torch(x6.reshape(-1, 6))
+    R = A.to(x6) @ R.reshape(*x6.shape[:-1], 3, 3)
+    return torch.cat([R[..., :, 0], R[..., :, 1]], dim=-1)
+
+
+def reframe_joints(joints, J0, A, a, has_transl: bool):
+    """joints [...,J,3] of a body through p -> A p + a: A j + a when the parameters carry a translation; A (j - J0) + J0 when they
+    do not (``predict_transl`` false, and rot6d, which is posed with zero betas and no translation): only the orientation can be
+    re-framed then, and this is what the SMPL joints of the re-framed parameters are.  J0, a [...,3], A [...,3,3] broadcast over the
+    leading dimensions of joints (the joint axis excluded)."""
+    A = A.to(joints)[..., None, :, :]
+    if has_transl:
+        return _apply(A, joints) + a.to(joints)[..., None, :]
+    J0 = J0.to(joints)[..., None, :]
+    return _apply(A, joints - J0) + J0
+
+
 # ----------------------------------------------------------------------------- kernels
 _WS: Dict[tuple, torch.Tensor] = {}
 
@@ -260,18 +379,51 @@ def stitch_windows_hip(feats, overlap: int, n_frames: int, layout: int) -> torch
     return out
 
 
+def scene_views_hip(verts, world2view, P: int) -> Dict[str, torch.Tensor]:
+    """verts [N,3], world2view [W,4,4] fp32 on the device -> cloud [W,P,3], index [W,P] int32, count [W] int32
+    (``seeme_scene_views``).  Launches on the current stream and does not synchronise."""
+    L.require_cuda(verts, "verts")
+    L.require_cuda(world2view, "world2view")
+    if verts.dim() != 2 or verts.shape[1] != 3 or world2view.dim() != 3 or tuple(world2view.shape[1:]) != (4, 4):
+        raise L.SeemeError(f"scene_views: verts are {tuple(verts.shape)}, world2view is {tuple(world2view.shape)}: expected [N,3] and [W,4,4]")
+    return _launch_scene_views(verts.contiguous(), world2view.contiguous(), int(P))
+
+
+def _launch_scene_views(verts, M, P, ws=None, ws_bytes=None, out=None) -> Dict[str, torch.Tensor]:
+    """ws / ws_bytes: another workspace and the size to state for it; out: (cloud, index, count) to write into (the tests' slots)."""
+    dev = verts.device
+    N, W = int(verts.shape[0]), int(M.shape[0])
+    lib = L.lib()
+    need = int(lib.seeme_scene_views_workspace_bytes(N, W, P))
+    if ws is None:
+        ws = _workspace(dev, need)
+    if out is None:
+        out = (torch.empty(W, max(P, 0), 3, device=dev, dtype=torch.float32), torch.empty(W, max(P, 0), device=dev, dtype=torch.int32),
+               torch.empty(W, device=dev, dtype=torch.int32))
+    cloud, index, count = out
+    L.check(lib.seeme_scene_views(verts.data_ptr(), M.data_ptr(), N, W, P, cloud.data_ptr(), index.data_ptr(), count.data_ptr(),
+                                  ws.data_ptr(), need if ws_bytes is None else ws_bytes, L.current_stream()), "seeme_scene_views")
+    return {"cloud": cloud, "index": index, "count": count}
+
+
 # ----------------------------------------------------------------------------- recording files
 _REC_KEYS = ("global_orient", "body_pose", "transl", "betas")
 
 
 def load_recording(path: str) -> Dict[str, np.ndarray]:
     """A recording ``.npz`` (read with allow_pickle=False: an object array is refused): the INTERACTEE's global_orient [L,3],
-    body_pose [L,69|63], transl [L,3], betas [10]; optionally scene [P,3], image_feats [L,2048], wearer_betas [10].  float32."""
+    body_pose [L,69|63], transl [L,3], betas [10]; optionally scene [P,3], image_feats [L,2048], wearer_betas [10].  float32.
+    A moving camera adds world2cam [L,4,4], the rigid map from the recording's world frame to every frame's camera frame (float64:
+    it is composed and inverted), and, in place of scene, scene_vertices [N,3]: the scene's vertices in the world frame, from which
+    every window's view is selected (``scene_views_hip``)."""
     with np.load(path, allow_pickle=False) as z:
         missing = [k for k in _REC_KEYS if k not in z.files]
         if missing:
             raise ValueError(f"{path}: missing {missing}; a recording holds {list(_REC_KEYS)} of the interactee")
-        rec = {k: np.asarray(z[k], np.float32) for k in _REC_KEYS + ("scene", "image_feats", "wearer_betas") if k in z.files}
+        rec = {k: np.asarray(z[k], np.float32) for k in _REC_KEYS + ("scene", "image_feats", "wearer_betas", "scene_vertices")
+               if k in z.files}
+        if "world2cam" in z.files:
+            rec["world2cam"] = np.asarray(z["world2cam"], np.float64)
     n = rec["global_orient"].shape[0]
     want = {"global_orient": [(n, 3)], "body_pose": [(n, 69), (n, 63)], "transl": [(n, 3)], "betas": [(10,)], "wearer_betas": [(10,)],
             "image_feats": [(n, 2048)]}
@@ -282,8 +434,33 @@ def load_recording(path: str) -> Dict[str, np.ndarray]:
             raise ValueError(f"{path}: {k} is {rec[k].shape}: expected {' or '.join(str(list(s)) for s in shapes)} (L = {n})")
     if "scene" in rec and (rec["scene"].ndim != 2 or rec["scene"].shape[1] != 3 or rec["scene"].shape[0] < 1):
         raise ValueError(f"{path}: scene is {rec['scene'].shape}: expected [P,3]")
+    if "scene_vertices" in rec and (rec["scene_vertices"].ndim != 2 or rec["scene_vertices"].shape[1] != 3 or rec["scene_vertices"].shape[0] < 1):
+        raise ValueError(f"{path}: scene_vertices is {rec['scene_vertices'].shape}: expected [N,3]")
+    if "scene_vertices" in rec and "scene" in rec:
+        raise ValueError(f"{path}: holds both scene and scene_vertices; a recording has ONE scene: a fixed cloud, or the vertices "
+                         "every window's view is selected from")
+    if "scene_vertices" in rec and "world2cam" not in rec:
+        raise ValueError(f"{path}: scene_vertices need world2cam: a view is selected per camera pose")
+    if "world2cam" in rec:
+        check_world2cam(rec["world2cam"], n, path)
     rec["n_frames"] = n
     return rec
+
+
+def check_world2cam(M, n_frames: int, what: str = "world2cam") -> None:
+    """[L,4,4] rigid maps: last row 0 0 0 1, the 3x3 block orthonormal to 1e-3 with a positive determinant; a ValueError names the
+    first frame that is not."""
+    M = np.asarray(M, np.float64)
+    if M.shape != (n_frames, 4, 4):
+        raise ValueError(f"{what}: world2cam is {M.shape}: expected [{n_frames},4,4] (L = {n_frames})")
+    A = M[:, :3, :3]
+    bad = (np.abs(M[:, 3] - np.array([0.0, 0.0, 0.0, 1.0])).max(axis=1) > 1e-6) | ~np.isfinite(M).all(axis=(1, 2))
+    with np.errstate(invalid="ignore"):
+        bad |= ~(np.abs(A.transpose(0, 2, 1) @ A - np.eye(3)).max(axis=(1, 2)) <= 1e-3) | ~(np.linalg.det(np.nan_to_num(A)) > 0)
+    if bad.any():
+        f = int(np.argmax(bad))
+        raise ValueError(f"{what}: world2cam of frame {f} is not a rigid map (last row 0 0 0 1, a rotation to 1e-3 with a positive "
+                         f"determinant):\n{M[f]}")
 
 
 def _stats_of(dm_or_stats):
@@ -299,12 +476,20 @@ def _stats_of(dm_or_stats):
 
 
 def windows_batch(rec, datamodule_or_stats, T: int, overlap: int, condition, dataset: Optional[str] = None,
-                  data_type: Optional[str] = None, predict_transl: bool = True, device=None):
+                  data_type: Optional[str] = None, predict_transl: bool = True, device=None, world2cam=None,
+                  scene_points: Optional[int] = None, pelvis=None):
     """The W windows of a recording as ONE batch with the data module's tuple layout (``mld.split_batch``): motion [W,T,2,D], transl
     [W,2,T,3], beta [W,2,T,10], utils [W,T,6], [scene [W,P,3]], [images [W,2048]], length [W,1].  The interactee (slot 1) is
     normalised by the rule the data module applies at load time (``data.normalise_person`` / ``data.normalise_rot6d``: zero padding to
     T first); the wearer's slot (0) is all zeros.  A window's image features are those of its centre frame.  Returns (batch, starts,
-    lengths).  datamodule_or_stats: a data module (``mean`` / ``std``) or the pair (mean, std)."""
+    lengths).  datamodule_or_stats: a data module (``mean`` / ``std``) or the pair (mean, std).
+
+    A moving camera: world2cam [L,4,4] (default: the recording's own key; without either nothing changes).  Window w is then put
+    into the camera frame of its first frame, M_w = world2cam[starts[w]], as the data module does for training: the interactee's
+    global_orient / transl are re-framed by M_w (``reframe_smpl``, float64, about `pelvis` [3] = ``rest_pelvis`` of the interactee's
+    betas) before the normalisation, and the scene slot holds each window's own view: ``scene_views_hip`` of the recording's
+    scene_vertices with `scene_points` rows (default 20000; needs `device`), or the fixed scene cloud moved by M_w.  Returns
+    (batch, starts, lengths, frames) with frames = {"world2cam": M [W,4,4] float64, "scene_view_count": count [W] int32 or None}."""
     from .data import load_time_stats, normalise_person, normalise_rot6d
     mean, std, dm_name, dm_type = _stats_of(datamodule_or_stats)
     n = int(rec["n_frames"])
@@ -317,12 +502,26 @@ def windows_batch(rec, datamodule_or_stats, T: int, overlap: int, condition, dat
     starts, lengths = window_plan(n, T, overlap)
     W = len(starts)
     m, s = load_time_stats(mean, std, rot6d)
+    w2c = world2cam if world2cam is not None else rec.get("world2cam")
+    if w2c is not None:
+        check_world2cam(w2c, n, "windows_batch")
+        if pelvis is None:
+            raise ValueError("windows_batch: world2cam needs pelvis [3], the interactee's rest pelvis (recording.rest_pelvis): SMPL "
+                             "rotates about it, so the translation cannot be re-framed without it")
+        Mw = torch.from_numpy(np.asarray(w2c, np.float64)[starts])                                  # [W,4,4]
+        J0 = torch.as_tensor(pelvis).detach().double().cpu().reshape(3)
+    elif "scene_vertices" in rec:
+        raise ValueError("windows_batch: scene_vertices need world2cam: a view is selected per camera pose")
     motion = np.zeros((W, T, 2, 3 + P), np.float32)
     transl = np.zeros((W, 2, T, 3), np.float32)
     beta = np.zeros((W, 2, T, 10), np.float32)
     for w, (lo, ln) in enumerate(zip(starts, lengths)):
         go, bp, tr = np.zeros((T, 3), np.float32), np.zeros((T, P), np.float32), np.zeros((T, 3), np.float32)
         go[:ln], bp[:ln], tr[:ln] = rec["global_orient"][lo:lo + ln], rec["body_pose"][lo:lo + ln], rec["transl"][lo:lo + ln]
+        if w2c is not None:
+            A, a = rigid_parts(Mw[w])
+            go_w, tr_w = reframe_smpl(torch.from_numpy(go[:ln]).double(), torch.from_numpy(tr[:ln]).double(), J0, A, a)
+            go[:ln], tr[:ln] = go_w.float().numpy(), tr_w.float().numpy()
         motion[w, :, 1], transl[w, 1] = normalise_person(go, bp, tr, m, s, dataset, bool(predict_transl) and not rot6d)
         beta[w, 1, :ln] = rec["betas"]
     length = torch.tensor(lengths, dtype=torch.long).reshape(W, 1)
@@ -331,10 +530,22 @@ def windows_batch(rec, datamodule_or_stats, T: int, overlap: int, condition, dat
         motion_t = normalise_rot6d(motion_t, length, mean, std)
         motion_t[:, :, 0] = 0.0                                                # the wearer's slot stays zero
     out = [motion_t, torch.from_numpy(transl), torch.from_numpy(beta), torch.zeros(W, T, 6)]
+    view_count = None
     if "scene" in condition:
-        if "scene" not in rec:
+        if "scene_vertices" in rec:
+            if device is None or torch.device(device).type != "cuda":
+                raise ValueError("windows_batch: the views of scene_vertices are selected by seeme_scene_views: pass the ROCm device")
+            npts = SCENE_VIEW_POINTS if scene_points is None else int(scene_points)
+            views = scene_views_hip(torch.from_numpy(rec["scene_vertices"]).to(device), Mw.float().to(device), npts)
+            out.append(views["cloud"])
+            view_count = views["count"]
+        elif "scene" not in rec:
             raise ValueError("windows_batch: the model has a 'scene' condition and the recording holds no scene cloud")
-        out.append(torch.from_numpy(rec["scene"])[None].expand(W, -1, -1).contiguous())
+        elif w2c is not None:                                                  # the fixed cloud, moved into each window's frame
+            A, a = rigid_parts(Mw)
+            out.append((torch.from_numpy(rec["scene"]).double()[None] @ A.transpose(1, 2) + a[:, None]).float().contiguous())
+        else:
+            out.append(torch.from_numpy(rec["scene"])[None].expand(W, -1, -1).contiguous())
     if "image" in condition:
         if "image_feats" not in rec:
             raise ValueError("windows_batch: the model has an 'image' condition and the recording holds no image_feats")
@@ -343,4 +554,6 @@ def windows_batch(rec, datamodule_or_stats, T: int, overlap: int, condition, dat
     out.append(length)
     if device is not None:
         out = [t.to(device) for t in out]
+    if w2c is not None:
+        return tuple(out), starts, lengths, {"world2cam": Mw, "scene_view_count": view_count}
     return tuple(out), starts, lengths
