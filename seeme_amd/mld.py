@@ -19,6 +19,9 @@ What runs where
   * Only the live flows are implemented; the reference's dead code (``forward`` calling the undefined
     ``feats2joints``, t2m_eval, the ``save_for_edo`` debug dump -- SURVEY.md App. D) is not reproduced:
     ``forward``/``sample`` = what ``ego_eval`` really does (condition -> reverse diffusion -> decode).
+  * Sampling is one set of steps with three callers (``ego_eval`` at K = 1, ``_ego_eval_hypotheses`` for K > 1, ``predict``):
+    ``_condition_tokens`` -> ``_posterior_draws`` / ``_condition_rows`` -> ``_diffusion_reverse`` (one launch) or
+    ``_diffusion_reverse_rows`` (at most 512 rows per launch) -> one decode or ``_decode_rows``.
   * The image condition takes the ResNet-50 backbone's pooled features [B,2048] in the batch's image slot or, with
     ``model.image_backbone``, the crops themselves (the backbone then runs here, frozen and in eval mode: seeme_amd/resnet.py);
     ``output_images`` is trainable and its stage-2 forward / gradient are glue problems, evaluation projects with a torch op.
@@ -615,7 +618,70 @@ class MLD(nn.Module):
             eps = torch.empty_like(mu).normal_()
         return mu + eps.to(mu) * std, normal
 
+    # ------------------------------------------------------------------ the sampling steps of ego_eval and predict
+    @staticmethod
+    def _rep_rows(t, K: int):
+        """[1,B,256] -> [1,B*K,256], row b*K + k = row b; K = 1 is `t` itself (no launch)."""
+        return t if K == 1 else t.repeat_interleave(K, dim=1)
+
+    def _condition_tokens(self, scene, images, K: int, who: str):
+        """(scene_tok, img_tok) of a sampling pass, each [1,B*K,256] or None; scene_tok is [1,2*B*K,256] under guidance.  The encoders
+        run once per sequence, on B rows, and the tokens are repeated K times.  Stage 'vae' conditions on nothing.  `who` names the
+        caller in the error message."""
+        scene_tok = img_tok = None
+        if self.stage == "vae":
+            return scene_tok, img_tok
+        if images is not None:
+            if self.do_classifier_free_guidance:
+                raise NotImplementedError(f"{who} with an 'image' condition and guidance_scale > 1: the reference builds no unconditional "
+                                          "scene / image token in the image branches of ego_eval (mld.py:1076-1100) while _diffusion_reverse "
+                                          "halves the batch (:437-438), so that configuration cannot run; training with it is defined (DESIGN 6a)")
+            img_tok = self._rep_rows(self._image_token(images), K)         # (no unconditional image token: see above)
+            if scene is not None:
+                scene_tok = self._rep_rows(self._scene_token(scene), K)
+        elif scene is not None:
+            scene_tok = self._rep_rows(self._scene_token(scene), K)
+            if self.do_classifier_free_guidance:                           # zero-scene branch (:1144-1158)
+                unc = self._rep_rows(self._scene_token(torch.zeros_like(scene)), K)
+                # the reference concatenates [scene, scene_uncond] while _diffusion_reverse takes the FIRST half as
+                # unconditional (:489): reproduced by default, TEST.CFG_SCENE_ORDER 'fixed' puts uncond first
+                scene_tok = torch.cat([scene_tok, unc] if self.cfg_scene_order == "reference" else [unc, scene_tok], dim=1)
+        return scene_tok, img_tok
+
+    def _posterior_draws(self, feats, lengths, eps, K: int):
+        """K posterior draws per sequence from ONE encode: [1,B*K,256], the posterior mean under TEST.SAMPLE_MEAN.  eps [1,B*K,256]
+        replaces the draw.  For K = 1 this is _sample_latent without the Normal object."""
+        dist = self.vae.encode_dist(feats, lengths)
+        mu, std = self._rep_rows(dist[0:1], K), self._rep_rows(dist[1:2].exp().pow(0.5), K)
+        if self.sample_mean:
+            return mu
+        if eps is None:
+            eps = torch.empty_like(mu).normal_()
+        return mu + eps.to(mu).reshape(mu.shape) * std
+
+    def _condition_rows(self, f_int, lengths, eps_c, eps_u, scene_tok, img_tok, K: int):
+        """The denoiser's condition, batch-first [B*K or 2*B*K, N, 256] (unconditional rows first with guidance): the tokens
+        [text, scene, images] (:1297-1306), text = K draws of the interactee's posterior (f_int None: no such token; :1271-1295)."""
+        text_emb = None
+        if f_int is not None:
+            text_emb = self._posterior_draws(f_int, lengths, eps_c, K)
+            if self.do_classifier_free_guidance:
+                text_emb = torch.cat([self._posterior_draws(torch.zeros_like(f_int), lengths, eps_u, K), text_emb], dim=1)
+        toks = [t for t in (text_emb, scene_tok, img_tok) if t is not None]
+        if not toks:
+            raise ValueError("no condition tokens")
+        return torch.cat(toks, dim=0).permute(1, 0, 2)
+
     # ------------------------------------------------------------------ reverse diffusion (mld.py:432-511)
+    def _reverse_setup(self, latents):
+        """The initial latents scaled for the scheduler, whose inference timesteps are set here, and the eta of its step."""
+        latents = latents * self.scheduler.init_noise_sigma
+        self.scheduler.set_timesteps(self.cfg.model.scheduler.num_inference_timesteps)
+        eta = 0.0
+        if "eta" in set(inspect.signature(self.scheduler.step).parameters.keys()):
+            eta = self.cfg.model.scheduler.eta
+        return latents, eta
+
     def _diffusion_reverse(self, encoder_hidden_states, lengths=None, latents=None, step_noise=None):
         bsz = encoder_hidden_states.shape[0]
         if self.do_classifier_free_guidance:
@@ -623,11 +689,7 @@ class MLD(nn.Module):
         if latents is None:
             latents = torch.randn((bsz, self.latent_dim[0], self.latent_dim[-1]), device=encoder_hidden_states.device,
                                   dtype=torch.float)
-        latents = latents * self.scheduler.init_noise_sigma
-        self.scheduler.set_timesteps(self.cfg.model.scheduler.num_inference_timesteps)
-        eta = 0.0
-        if "eta" in set(inspect.signature(self.scheduler.step).parameters.keys()):
-            eta = self.cfg.model.scheduler.eta
+        latents, eta = self._reverse_setup(latents)
         # the 50 (or 1000) sequential denoiser calls + CFG + scheduler.step are ONE kernel launch
         return self.denoiser.sample_loop(latents, encoder_hidden_states.contiguous(), self.scheduler, eta=eta,
                                          guidance_scale=self.guidance_scale if self.do_classifier_free_guidance else 1.0,
@@ -881,54 +943,31 @@ class MLD(nn.Module):
         classifier-free guidance; step_noise for DDPM.
 
         num_hypotheses K (None: TEST.NUM_HYPOTHESES) > 1 draws K hypotheses per sequence from ONE encode of the condition
-        (``_ego_eval_hypotheses``): the injection points then have B*K rows, row b*K + k = hypothesis k of sequence b.  K = 1 is the
-        path below, unchanged.  hyp_select (None: TEST.HYP_SELECT) 'first' | 'medoid' chooses the hypothesis that fills the keys of a
-        K = 1 result; it applies only for K > 1."""
+        (``_ego_eval_hypotheses``): the injection points then have B*K rows, row b*K + k = hypothesis k of sequence b.  Both paths (and
+        ``predict``) build the condition with the same steps (``_condition_tokens``, ``_posterior_draws``, ``_condition_rows``); K = 1's
+        own, below, are the single sampling launch for any B (``_diffusion_reverse``) and the single decode.  hyp_select (None:
+        TEST.HYP_SELECT) 'first' | 'medoid' chooses the hypothesis that fills the keys of a K = 1 result; it applies only for K > 1."""
         K = self.num_hypotheses if num_hypotheses is None else self._check_num_hypotheses(num_hypotheses, "num_hypotheses")
         select = self.hyp_select if hyp_select is None else check_select(hyp_select, "hyp_select")
-        if K > 1:
-            return self._ego_eval_hypotheses(batch, K, latents, want_vertices, cond_noise, step_noise, select)
         int_gt = None
         if self.pose_estimation_task:       # batch ends with the interactee's ground truth (mld.py:1119-1131)
             batch, int_gt = tuple(batch[:-3]), tuple(t.float() for t in batch[-3:])
+        if K > 1:
+            return self._ego_eval_hypotheses(batch, int_gt, K, latents, want_vertices, cond_noise, step_noise, select)
         eps_c, eps_u = cond_noise if isinstance(cond_noise, (tuple, list)) else (cond_noise, None)
         # image layouts: `length` last, as the dataset hands it over (the reference's unpack at :1079 / :1093 omits it: DESIGN 6a)
         feats_ref, transl, beta, utils_, scene, images, length, _ = split_batch(self.condition, batch)
-        scene_tok = img_tok = None
-        if images is not None and self.stage != "vae":
-            if self.do_classifier_free_guidance:
-                raise NotImplementedError("ego_eval with an 'image' condition and guidance_scale > 1: the reference builds no unconditional "
-                                          "scene / image token in the image branches (mld.py:1076-1100) while _diffusion_reverse halves the "
-                                          "batch (:437-438), so that configuration cannot run; training with it is defined (DESIGN 6a)")
-            img_tok = self._image_token(images)                           # (no unconditional image token: see above)
-            if scene is not None:
-                scene_tok = self._scene_token(scene)
-        elif scene is not None and self.stage != "vae":
-            scene_tok = self._scene_token(scene)
-            if self.do_classifier_free_guidance:                           # zero-scene branch (:1144-1158)
-                unc = self._scene_token(torch.zeros_like(scene))
-                # the reference concatenates [scene, scene_uncond] while _diffusion_reverse takes the FIRST half as
-                # unconditional (:489): reproduced by default, TEST.CFG_SCENE_ORDER 'fixed' puts uncond first
-                scene_tok = torch.cat([scene_tok, unc] if self.cfg_scene_order == "reference" else [unc, scene_tok], dim=1)
+        scene_tok, img_tok = self._condition_tokens(scene, images, 1, "ego_eval")
         feats_ref, transl, beta = feats_ref.float(), transl.float(), beta.float()
         lengths = length.long().reshape(-1).tolist()
         idx_ref = 0 if self.estimate == "wearer" else 1
         start = time.time()
         if self.stage in ("diffusion", "vae_diffusion"):
-            text_emb = None
-            if "interactee" in self.condition:                             # :1271-1295
-                f_int = self._wearer_features(feats_ref, transl, 1)
-                text_emb, _ = self._sample_latent(f_int, lengths, eps_c, mean=self.sample_mean)
-                if self.do_classifier_free_guidance:
-                    unc, _ = self._sample_latent(torch.zeros_like(f_int), lengths, eps_u, mean=self.sample_mean)
-                    text_emb = torch.cat([unc, text_emb], dim=1)
-            toks = [t for t in (text_emb, scene_tok, img_tok) if t is not None]      # :1297-1306: [text, scene, images]
-            if not toks:
-                raise ValueError("no condition tokens")
-            cond_emb = torch.cat(toks, dim=0)                               # [N, B or 2B, 256]
-            z = self._diffusion_reverse(cond_emb.permute(1, 0, 2), lengths, latents=latents, step_noise=step_noise)
+            f_int = self._wearer_features(feats_ref, transl, 1) if "interactee" in self.condition else None
+            cond_bf = self._condition_rows(f_int, lengths, eps_c, eps_u, scene_tok, img_tok, 1)      # [B or 2B, N, 256]
+            z = self._diffusion_reverse(cond_bf, lengths, latents=latents, step_noise=step_noise)
         elif self.stage == "vae":                                          # :1328-1352: reconstruction of the target itself
-            z, _ = self._sample_latent(self._wearer_features(feats_ref, transl, idx_ref), lengths, eps_c, mean=self.sample_mean)
+            z = self._posterior_draws(self._wearer_features(feats_ref, transl, idx_ref), lengths, eps_c, 1)
         else:
             raise ValueError(f"Not support this stage {self.stage}!")
         if self.see_future:
@@ -946,26 +985,33 @@ class MLD(nn.Module):
         joints_ref, joints_rst = (out_ref[0], out_rst[0]) if want_vertices else (out_ref, out_rst)
         f_int_r = self.renorm(self._wearer_features(feats_ref[:, :min_len], transl[:, :, :min_len], 1))
         joints_int = self._feats_to_joints(f_int_r, beta[:, 1, :min_len])
-        joints_int_gt = None
-        if int_gt is not None:              # mld.py:1843-1866: SMPL joints of the interactee's ground-truth motion
-            g_motion, g_transl, _g_beta = int_gt
-            f_gt = g_motion[:, :min_len, 0]
-            if self.transl_in_feats:
-                f_gt = torch.cat([f_gt, g_transl[:, 0, :min_len]], dim=-1)
-            joints_int_gt = self._feats_to_joints(self.renorm(f_gt.contiguous()), beta[:, 1, :min_len])
-        if self.data_type == "angle":
-            quat = lambda f, o=None: G.aa_to_quat((f[:, :, :3] if o is None else o).reshape(-1, 3).contiguous())
-        else:
-            quat = lambda f, o=None: None
+        joints_int_gt = self._interactee_gt_joints(int_gt, beta, min_len)
         rs = {"m_ref": f_ref, "m_rst": f_rst, "joints_ref": joints_ref, "joints_rst": joints_rst,
-              "orientation_quat_rst": quat(f_rst, o_rst), "orientation_quat_ref": quat(f_ref),
+              "orientation_quat_rst": self._orientation_quat(f_rst, o_rst), "orientation_quat_ref": self._orientation_quat(f_ref),
               "root_interactee": joints_int[:, :, 0], "joints_interactee": joints_int,
-              "orientation_quat_int": quat(f_int_r), "joints_interactee_gt": joints_int_gt, "lengths": lengths,
+              "orientation_quat_int": self._orientation_quat(f_int_r), "joints_interactee_gt": joints_int_gt, "lengths": lengths,
               "list_names": {}, "lat_t": z}
         if want_vertices:
             rs["vertices_ref"], rs["vertices_rst"] = out_ref[1], out_rst[1]
         self._add_mesh_results(rs, f_rst, f_ref, b_ref, o_rst, lengths, 1, scene)
         return rs
+
+    def _interactee_gt_joints(self, int_gt, beta, min_len):
+        """SMPL joints of the interactee's ground-truth motion (TEST.POSE_ESTIMATION_TASK, mld.py:1843-1866); None without it."""
+        if int_gt is None:
+            return None
+        g_motion, g_transl, _g_beta = int_gt
+        f_gt = g_motion[:, :min_len, 0]
+        if self.transl_in_feats:
+            f_gt = torch.cat([f_gt, g_transl[:, 0, :min_len]], dim=-1)
+        return self._feats_to_joints(self.renorm(f_gt.contiguous()), beta[:, 1, :min_len])
+
+    def _orientation_quat(self, f, o=None):
+        """[rows*T,4] quaternions of the global orientation of renormed 'angle' features [rows,T,F], or of `o` [rows,T,3] in its
+        place; None for other data types."""
+        if self.data_type != "angle":
+            return None
+        return G.aa_to_quat((f[:, :, :3] if o is None else o).reshape(-1, 3).contiguous())
 
     def _mesh_metrics(self, f_rst, f_ref, b_ref, orient, lengths, K, scene, mesh=True, collision=False):
         """TEST.MESH_METRICS: PA_MPJPE, V2V [B,K] and, with a scene in the batch, SCENE_DIST, CONTACT_RATIO [B,K] and their _REF
@@ -1018,11 +1064,7 @@ class MLD(nn.Module):
         dev = cond_bf.device
         if latents is None:
             latents = torch.randn((rows, self.latent_dim[0], self.latent_dim[-1]), device=dev, dtype=torch.float)
-        latents = latents * self.scheduler.init_noise_sigma
-        self.scheduler.set_timesteps(self.cfg.model.scheduler.num_inference_timesteps)
-        eta = 0.0
-        if "eta" in set(inspect.signature(self.scheduler.step).parameters.keys()):
-            eta = self.cfg.model.scheduler.eta
+        latents, eta = self._reverse_setup(latents)
         if self.scheduler.needs_noise(eta):
             steps = len(self.scheduler.timesteps)
             if step_noise is None:
@@ -1039,76 +1081,19 @@ class MLD(nn.Module):
                                                  step_noise=None if step_noise is None else step_noise[:, lo:hi]))
         return out[0] if len(out) == 1 else torch.cat(out, dim=1)            # [1,rows,256]
 
-    def _ego_eval_hypotheses(self, batch, K, latents=None, want_vertices=False, cond_noise=None, step_noise=None, select="first"):
-        """ego_eval for K > 1.  Once per SEQUENCE: the PointNet scene code and its token (and the zero-scene token under guidance),
-        the image token, vae.encode_dist of the interactee (and of the zero motion), the reference and interactee joints.  Per
-        HYPOTHESIS: the posterior draw of the condition token, the initial latent, the DDPM step noise, decode, renorm, SMPL joints.
-        Rows are sequence-major (b*K + k).  The keys of the K = 1 result are filled from hypothesis 0, or with select 'medoid' from
-        the medoid of the K draws of each sequence (hm gains PAIR_DIST, medoid_index and selected_index)."""
-        int_gt = None
-        if self.pose_estimation_task:
-            batch, int_gt = tuple(batch[:-3]), tuple(t.float() for t in batch[-3:])
-        eps_c, eps_u = cond_noise if isinstance(cond_noise, (tuple, list)) else (cond_noise, None)
-        feats_ref, transl, beta, utils_, scene, images, length, _ = split_batch(self.condition, batch)
-        B = feats_ref.shape[0]
-        BK = B * K
-        rep = lambda t: t.repeat_interleave(K, dim=1)                       # [1,B,256] -> [1,B*K,256]
-        scene_tok = img_tok = None
-        if images is not None and self.stage != "vae":
-            if self.do_classifier_free_guidance:
-                raise NotImplementedError("ego_eval with an 'image' condition and guidance_scale > 1 (see ego_eval)")
-            img_tok = rep(self._image_token(images))
-            if scene is not None:
-                scene_tok = rep(self._scene_token(scene))
-        elif scene is not None and self.stage != "vae":
-            scene_tok = rep(self._scene_token(scene))
-            if self.do_classifier_free_guidance:                           # halves in the order of ego_eval (TEST.CFG_SCENE_ORDER)
-                unc = rep(self._scene_token(torch.zeros_like(scene)))
-                scene_tok = torch.cat([scene_tok, unc] if self.cfg_scene_order == "reference" else [unc, scene_tok], dim=1)
-        feats_ref, transl, beta = feats_ref.float(), transl.float(), beta.float()
-        lengths = length.long().reshape(-1).tolist()
-        idx_ref = 0 if self.estimate == "wearer" else 1
-
-        def draws(feats, eps):
-            """K posterior draws per sequence from ONE encode: [1,B*K,256]."""
-            dist = self.vae.encode_dist(feats, lengths)
-            mu, std = rep(dist[0:1]), rep(dist[1:2].exp().pow(0.5))
-            if self.sample_mean:
-                return mu
-            if eps is None:
-                eps = torch.empty_like(mu).normal_()
-            return mu + eps.to(mu).reshape(1, BK, -1) * std
-
-        start = time.time()
-        if self.stage in ("diffusion", "vae_diffusion"):
-            text_emb = None
-            if "interactee" in self.condition:
-                f_int = self._wearer_features(feats_ref, transl, 1)
-                text_emb = draws(f_int, eps_c)
-                if self.do_classifier_free_guidance:
-                    text_emb = torch.cat([draws(torch.zeros_like(f_int), eps_u), text_emb], dim=1)
-            toks = [t for t in (text_emb, scene_tok, img_tok) if t is not None]
-            if not toks:
-                raise ValueError("no condition tokens")
-            cond_emb = torch.cat(toks, dim=0)                               # [N, B*K or 2*B*K, 256]
-            z = self._diffusion_reverse_rows(cond_emb.permute(1, 0, 2), BK, latents=latents, step_noise=step_noise)
-        elif self.stage == "vae":                                          # K posterior draws of the target
-            z = draws(self._wearer_features(feats_ref, transl, idx_ref), eps_c)
-        else:
-            raise ValueError(f"Not support this stage {self.stage}!")
-        if self.see_future:
-            lengths = [int(i // 2) for i in lengths]
-        min_len = min(feats_ref.shape[1], int(max(lengths)))
-        f_ref = self.renorm(self._wearer_features(feats_ref[:, :min_len], transl[:, :, :min_len], idx_ref))
-        b_ref = beta[:, idx_ref, :min_len]
-        o_ref = f_ref[:, :, :3] if (self.data_type == "angle" and self.name_dataset == "egobody" and not self.pred_global_orient) else None
-        dev = f_ref.device
+    def _decode_rows(self, z, lengths, K, min_len, betas, orient=None, start=None):
+        """Decode, renorm and pose the B*K latents z [1,B*K,256] (row b*K + k), at most MAX_SAMPLE_ROWS rows at a time: (f_rst
+        [B*K,min_len,F] renormed, zeros past what a chunk decodes, joints [B*K,min_len,24,3]).  betas [B,min_len,10] and orient
+        [B,min_len,3] or None are per sequence.  Every chunk is decoded before the first is posed; `start`, the time.time() at which
+        the caller's pass began, puts the time up to there into self.times (encode + sample + decode, mld.py:1367-1368)."""
+        rows, dev = z.shape[1], z.device
         lengths_k = [l for l in lengths for _ in range(K)]
-        f_rst = torch.zeros(BK, min_len, f_ref.shape[-1], device=dev, dtype=torch.float32)
-        joints_all = torch.empty(BK, min_len, 24, 3, device=dev, dtype=torch.float32)
-        chunks = self._row_chunks(BK)                                       # decode, renorm, SMPL joints of <= 512 rows at a time
+        f_rst = torch.zeros(rows, min_len, self.vae.nfeats, device=dev, dtype=torch.float32)
+        joints = torch.empty(rows, min_len, 24, 3, device=dev, dtype=torch.float32)
+        chunks = self._row_chunks(rows)
         decoded = [self.vae.decode(z[:, lo:hi], lengths_k[lo:hi]) for lo, hi in chunks]
-        self.times.append(time.time() - start)
+        if start is not None:
+            self.times.append(time.time() - start)
         for (lo, hi), feats_c in zip(chunks, decoded):                      # feats_c [n, max length of the chunk, F], zeros past each length
             tc = min(min_len, feats_c.shape[1])
             if tc == min_len:
@@ -1119,26 +1104,48 @@ class MLD(nn.Module):
             fc = self.renorm(fc)
             seq = torch.arange(lo, hi, device=dev) // K
             f_rst[lo:hi] = fc
-            joints_all[lo:hi] = self._feats_to_joints(fc, b_ref[seq], orient=None if o_ref is None else o_ref[seq])
-        del decoded
+            joints[lo:hi] = self._feats_to_joints(fc, betas[seq], orient=None if orient is None else orient[seq])
+        return f_rst, joints
+
+    def _ego_eval_hypotheses(self, batch, int_gt, K, latents=None, want_vertices=False, cond_noise=None, step_noise=None, select="first"):
+        """ego_eval for K > 1 (`int_gt`: what ego_eval split off the batch under TEST.POSE_ESTIMATION_TASK).  Once per SEQUENCE: the
+        PointNet scene code and its token (and the zero-scene token under guidance), the image token, vae.encode_dist of the
+        interactee (and of the zero motion), the reference and interactee joints.  Per HYPOTHESIS: the posterior draw of the
+        condition token, the initial latent, the DDPM step noise, decode, renorm, SMPL joints.
+        Rows are sequence-major (b*K + k).  The keys of the K = 1 result are filled from hypothesis 0, or with select 'medoid' from
+        the medoid of the K draws of each sequence (hm gains PAIR_DIST, medoid_index and selected_index)."""
+        eps_c, eps_u = cond_noise if isinstance(cond_noise, (tuple, list)) else (cond_noise, None)
+        feats_ref, transl, beta, utils_, scene, images, length, _ = split_batch(self.condition, batch)
+        B = feats_ref.shape[0]
+        scene_tok, img_tok = self._condition_tokens(scene, images, K, "ego_eval")
+        feats_ref, transl, beta = feats_ref.float(), transl.float(), beta.float()
+        lengths = length.long().reshape(-1).tolist()
+        idx_ref = 0 if self.estimate == "wearer" else 1
+        start = time.time()
+        if self.stage in ("diffusion", "vae_diffusion"):
+            f_int = self._wearer_features(feats_ref, transl, 1) if "interactee" in self.condition else None
+            cond_bf = self._condition_rows(f_int, lengths, eps_c, eps_u, scene_tok, img_tok, K)      # [B*K or 2*B*K, N, 256]
+            z = self._diffusion_reverse_rows(cond_bf, B * K, latents=latents, step_noise=step_noise)
+        elif self.stage == "vae":                                          # K posterior draws of the target
+            z = self._posterior_draws(self._wearer_features(feats_ref, transl, idx_ref), lengths, eps_c, K)
+        else:
+            raise ValueError(f"Not support this stage {self.stage}!")
+        if self.see_future:
+            lengths = [int(i // 2) for i in lengths]
+        min_len = min(feats_ref.shape[1], int(max(lengths)))
+        f_ref = self.renorm(self._wearer_features(feats_ref[:, :min_len], transl[:, :, :min_len], idx_ref))
+        b_ref = beta[:, idx_ref, :min_len]
+        o_ref = f_ref[:, :, :3] if (self.data_type == "angle" and self.name_dataset == "egobody" and not self.pred_global_orient) else None
+        dev = f_ref.device
+        f_rst, joints_all = self._decode_rows(z, lengths, K, min_len, b_ref, o_ref, start=start)
         out_ref = self._feats_to_joints(f_ref, b_ref, want_vertices)
         joints_ref = out_ref[0] if want_vertices else out_ref
         joints_all = joints_all.view(B, K, min_len, 24, 3)
         f_int_r = self.renorm(self._wearer_features(feats_ref[:, :min_len], transl[:, :, :min_len], 1))
         joints_int = self._feats_to_joints(f_int_r, beta[:, 1, :min_len])
-        joints_int_gt = None
-        if int_gt is not None:
-            g_motion, g_transl, _g_beta = int_gt
-            f_gt = g_motion[:, :min_len, 0]
-            if self.transl_in_feats:
-                f_gt = torch.cat([f_gt, g_transl[:, 0, :min_len]], dim=-1)
-            joints_int_gt = self._feats_to_joints(self.renorm(f_gt.contiguous()), beta[:, 1, :min_len])
-        if self.data_type == "angle":
-            quat = lambda f, o=None: G.aa_to_quat((f[:, :, :3] if o is None else o).reshape(-1, 3).contiguous())
-        else:
-            quat = lambda f, o=None: None
-        q_ref = quat(f_ref)
-        q_all = quat(f_rst, None if o_ref is None else o_ref.repeat_interleave(K, dim=0))      # [B*K*T,4]
+        joints_int_gt = self._interactee_gt_joints(int_gt, beta, min_len)
+        q_ref = self._orientation_quat(f_ref)
+        q_all = self._orientation_quat(f_rst, None if o_ref is None else o_ref.repeat_interleave(K, dim=0))      # [B*K*T,4]
         # per-hypothesis errors and the diversity of the K draws: one pass of seeme_hyp_metrics over the joints
         hm = hyp_metrics_hip(joints_all, joints_ref, lengths)
         lens = torch.as_tensor(lengths, device=dev).reshape(B)
@@ -1163,7 +1170,7 @@ class MLD(nn.Module):
               "orientation_quat_rst": None if q_all is None else pick(q_all.reshape(B, K, min_len, 4)).reshape(-1, 4),
               "orientation_quat_ref": q_ref,
               "root_interactee": joints_int[:, :, 0], "joints_interactee": joints_int,
-              "orientation_quat_int": quat(f_int_r), "joints_interactee_gt": joints_int_gt, "lengths": lengths,
+              "orientation_quat_int": self._orientation_quat(f_int_r), "joints_interactee_gt": joints_int_gt, "lengths": lengths,
               "list_names": {}, "lat_t": pick(z.view(B, K, -1))[None],
               "joints_rst_all": joints_all, "m_rst_all": f_rst.view(B, K, min_len, -1), "lat_t_all": z, "hyp_metrics": hm}
         self._add_mesh_results(rs, f_rst, f_ref, b_ref, o_ref, lengths, K, scene)
@@ -1191,45 +1198,17 @@ class MLD(nn.Module):
         eps_c, eps_u = cond_noise if isinstance(cond_noise, (tuple, list)) else (cond_noise, None)
         feats_ref, transl, beta, utils_, scene, images, length, _ = split_batch(self.condition, batch)
         B = feats_ref.shape[0]
-        BK = B * K
-        rep = lambda t: t.repeat_interleave(K, dim=1)                       # [1,B,256] -> [1,B*K,256]
-        scene_tok = img_tok = None
-        if images is not None:
-            if self.do_classifier_free_guidance:
-                raise NotImplementedError("predict with an 'image' condition and guidance_scale > 1 (see ego_eval)")
-            img_tok = rep(self._image_token(images))
-            if scene is not None:
-                scene_tok = rep(self._scene_token(scene))
-        elif scene is not None:
-            scene_tok = rep(self._scene_token(scene))
-            if self.do_classifier_free_guidance:                           # halves in the order of ego_eval (TEST.CFG_SCENE_ORDER)
-                unc = rep(self._scene_token(torch.zeros_like(scene)))
-                scene_tok = torch.cat([scene_tok, unc] if self.cfg_scene_order == "reference" else [unc, scene_tok], dim=1)
+        scene_tok, img_tok = self._condition_tokens(scene, images, K, "predict")
         lengths = length.long().reshape(-1).tolist()
         dev = feats_ref.device
-
-        def draws(feats, eps):
-            dist = self.vae.encode_dist(feats, lengths)
-            mu, std = rep(dist[0:1]), rep(dist[1:2].exp().pow(0.5))
-            if self.sample_mean:
-                return mu
-            if eps is None:
-                eps = torch.empty_like(mu).normal_()
-            return mu + eps.to(mu).reshape(1, BK, -1) * std
-
-        text_emb = None
+        f_int = None
         if "interactee" in self.condition:
             # the interactee's slot only: _wearer_features(.., 1) slices person 1 out of the motion and the translation
             # (cut to the longest sequence: the encoder builds its mask from max(lengths) -- a lone last window may be shorter than T)
             n_enc = min(int(feats_ref.shape[1]), int(max(lengths)))
             f_int = self._wearer_features(feats_ref[:, :n_enc, 1:2].float(), transl[:, 1:2, :n_enc].float(), 0)
-            text_emb = draws(f_int, eps_c)
-            if self.do_classifier_free_guidance:
-                text_emb = torch.cat([draws(torch.zeros_like(f_int), eps_u), text_emb], dim=1)
-        toks = [t for t in (text_emb, scene_tok, img_tok) if t is not None]
-        if not toks:
-            raise ValueError("no condition tokens")
-        z = self._diffusion_reverse_rows(torch.cat(toks, dim=0).permute(1, 0, 2), BK, latents=latents, step_noise=step_noise)
+        cond_bf = self._condition_rows(f_int, lengths, eps_c, eps_u, scene_tok, img_tok, K)
+        z = self._diffusion_reverse_rows(cond_bf, B * K, latents=latents, step_noise=step_noise)
         if self.see_future:
             lengths = [int(i // 2) for i in lengths]
         min_len = min(feats_ref.shape[1], int(max(lengths)))
@@ -1238,23 +1217,7 @@ class MLD(nn.Module):
         betas = torch.as_tensor(betas, device=dev, dtype=torch.float32)
         if tuple(betas.shape) != (B, 10):
             raise ValueError(f"predict: betas are {tuple(betas.shape)}: expected [B,10] = [{B},10]")
-        b_rst = betas[:, None, :].expand(B, min_len, 10)
-        F = self.vae.nfeats
-        lengths_k = [l for l in lengths for _ in range(K)]
-        f_rst = torch.zeros(BK, min_len, F, device=dev, dtype=torch.float32)
-        joints_all = torch.empty(BK, min_len, 24, 3, device=dev, dtype=torch.float32)
-        for lo, hi in self._row_chunks(BK):                                 # decode, renorm, SMPL joints of <= 512 rows at a time
-            feats_c = self.vae.decode(z[:, lo:hi], lengths_k[lo:hi])        # [n, max length of the chunk, F], zeros past each length
-            tc = min(min_len, feats_c.shape[1])
-            if tc == min_len:
-                fc = feats_c[:, :min_len].contiguous()
-            else:
-                fc = torch.zeros(hi - lo, min_len, F, device=dev, dtype=torch.float32)
-                fc[:, :tc] = feats_c[:, :tc]
-            fc = self.renorm(fc)
-            seq = torch.arange(lo, hi, device=dev) // K
-            f_rst[lo:hi] = fc
-            joints_all[lo:hi] = self._feats_to_joints(fc, b_rst[seq])
+        f_rst, joints_all = self._decode_rows(z, lengths, K, min_len, betas[:, None, :].expand(B, min_len, 10))
         joints_all = joints_all.view(B, K, min_len, 24, 3)
         return {"m_rst_all": f_rst.view(B, K, min_len, -1), "joints_rst_all": joints_all, "lat_t_all": z, "lengths": lengths,
                 "hyp_metrics": hyp_pairdist_hip(joints_all, lengths)}

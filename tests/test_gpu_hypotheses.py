@@ -398,3 +398,47 @@ def test_ego_eval_image_token_with_hypotheses(dev, condition):
         print(f"{condition} k={k}: {errs}")
         assert max(errs.values()) <= TOL_F32, (k, errs)
     assert float((rs["joints_rst_all"][:, 0] - rs["joints_rst_all"][:, 1]).abs().max()) > 1e-4
+
+
+# ----------------------------------------------------------------------------- the draws of a pass that is handed none
+def _steps10(cfg):
+    cfg.model.scheduler.num_inference_timesteps = 10
+
+
+def _guided10(cfg):
+    cfg.model.guidance_scale = 2.5
+    cfg.model.scheduler.num_inference_timesteps = 10
+
+
+@pytest.mark.parametrize("cfg_name,mutate,entry,B,K", [("config_mld_egobody.yaml", _steps10, "ego_eval", 3, 1),
+                                                      ("config_mld_egobody.yaml", _steps10, "ego_eval", 3, 4),
+                                                      ("config_mld_scene.yaml", _guided10, "ego_eval", 3, 3),
+                                                      ("config_mld_scene.yaml", _guided10, "predict", 3, 3),
+                                                      ("config_mld_egobody.yaml", _ddpm, "ego_eval", 2, 2)],
+                         ids=["egobody_k1", "egobody_k4", "scene_guided_k3", "scene_guided_predict_k3", "ddpm_k2"])
+def test_uninjected_pass_draws_in_the_documented_order(dev, cfg_name, mutate, entry, B, K):
+    """A pass that is handed no draws makes them on the device in this order and with these shapes: the condition's posterior noise
+    [1,B*K,256] (then the unconditional condition's under guidance), the initial latents [B*K,1,256], the DDPM step noise
+    [steps,B*K,256].  So the same draws, made by the same calls after the same seed and injected, give the same bits."""
+    model, dm, cfg = _mld(dev, cfg_name, mutate=mutate)
+    guidance = model.do_classifier_free_guidance
+    batch = dm.batch(B, idx=4, with_scene="scene" in cfg.model.condition, lengths=[16, 11, 16][:B])
+    run = lambda **kw: (model.predict if entry == "predict" else model.ego_eval)(batch, num_hypotheses=K, **kw)
+    seed = 1234
+    torch.manual_seed(seed)
+    eps_c = torch.empty(1, B * K, 256, device=dev).normal_()
+    cn = (eps_c, torch.empty(1, B * K, 256, device=dev).normal_()) if guidance else eps_c
+    lat = torch.randn(B * K, 1, 256, device=dev)
+    ddpm = mutate is _ddpm
+    noise = torch.randn(cfg.model.scheduler.num_inference_timesteps, B * K, 256, device=dev) if ddpm else None
+    fed = run(latents=lat, cond_noise=cn, step_noise=noise)
+    assert model.scheduler.needs_noise(0.0) == ddpm
+    torch.manual_seed(seed)
+    free = run()
+    keys = ("lat_t", "m_rst", "joints_rst") if K == 1 else ("lat_t_all", "m_rst_all", "joints_rst_all")
+    if entry == "ego_eval" and K > 1:
+        keys += ("lat_t", "m_rst", "joints_rst")
+    for key in keys:
+        assert torch.isfinite(fed[key]).all() and torch.equal(fed[key], free[key]), key
+    torch.manual_seed(seed + 1)                                       # (and the free pass does draw: another seed, another sample)
+    assert not torch.equal(run()[keys[0]], free[keys[0]])
