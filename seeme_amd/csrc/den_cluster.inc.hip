@@ -36,6 +36,10 @@
 // Weights: `units` of 8 waves x UL wave-loads x 1 KiB in order of use ([layer][CU][unit][wave][load][lane][16 B]); a wave-load
 // is the MFMA B operand of one (16-output tile, k-block) pair.  A ring of RU units in registers runs RU units (half a layer)
 // ahead of the consumer, across stage, layer and step boundaries.
+//
+// Who consumes a unit: all eight waves, each its eighth (fp32 images, C = 2 and 4, two condition tokens, k_den_cluster_ms) -- or, for the
+// 16-bit images at C = 8 with one condition token (the B <= 32 default), two groups of four waves that take the six GEMV phases in turn, so
+// that the group without a phase requests weights while the other computes (ClGrp below).  Same image, same sums, bit for bit.
 
 #define DCL_MAGIC_EPOCH 0x7fffffffu
 #define DCL_SPIN_LIMIT (1u << 22)
@@ -192,7 +196,8 @@ __device__ __forceinline__ void cl_refills(ClRing<WT>& ring, int wave, unsigned 
 }
 constexpr int cl_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// ---- the windowed load schedule (16-bit images, C = 8, one condition token).  Issuing a 1-KiB wave-load costs the CU's address path 16 cycles
+// ---- the windowed load schedule (every wave consumes every unit: k_den_cluster with two condition tokens or C = 4, and k_den_cluster_ms; the
+// 16-bit images at C = 8 with one condition token keep the windows and their flags but fill them by wave group, ClGrp below).  Issuing a 1-KiB wave-load costs the CU's address path 16 cycles
 // and the issuing wave waits its turn, so re-fills requested inline are exposed time: at a phase start every wave stands in the queue (phase B:
 // 2.4 k of its 4 k cycles), before a publish the stores stand behind them.  But while the epilogue wave is in an exchange or in its serial
 // vector algebra the other seven waves have nothing to do.  So they request ONE unit in each such window (56 KiB = 900 cycles of the path):
@@ -209,6 +214,7 @@ constexpr int cl_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? h
 template <int... Us> using ClSeq = std::integer_sequence<int, Us...>;
 template <int C, bool MF, bool Q> struct ClSched { static constexpr bool WIN = false; static constexpr int PRO = 0; typedef ClSeq<> W1A, W1B, W2A, W2B, WXA, WXB, W3, AF; };
 // "Just in time": a unit goes out in the window before the phase that consumes it; only the next layer's A is requested inline (after F).
+// (The <8, true, false> table is k_den_cluster_ms's at C = 8 since k_den_cluster runs that case on two wave groups.)
 // PRO: units in flight at a layer's start.  (Measured against it and dropped: "early", every unit one window ahead of the inline scheme, with
 // the next layer's B and C still inline in phase F; and just in time with two units in the second exchange window as well.)
 template <> struct ClSched<8, true, false> { static constexpr bool WIN = true; static constexpr int PRO = 2; typedef ClSeq<> WXA, WXB; typedef ClSeq<2, 3> W1A; typedef ClSeq<4> W1B; typedef ClSeq<5> W2A; typedef ClSeq<6> W2B;
@@ -234,6 +240,70 @@ typedef __attribute__((address_space(3))) volatile int cl_lds_flag;
 __device__ __forceinline__ void cl_flag_set(int* f, unsigned v) { *(cl_lds_flag*)f = (int)v; }
 __device__ __forceinline__ void cl_flag_wait(const int* f, unsigned v) {      // (set by this workgroup's epilogue wave: always arrives)
     while (*(const cl_lds_flag*)f != (int)v) __builtin_amdgcn_s_sleep(1);
+}
+
+// ---- two wave groups (16-bit images, C = 8, one condition token).  A GEMV phase needs four waves, one per SIMD: waves 0 .. 3 (G0, with the
+// epilogue wave) run A, C, E, waves 4 .. 7 (G1) run B, D, F.  The group without a phase is free to request weights while the vector-memory
+// path is otherwise idle, and its turn in the CU's in-order queue costs the chain nothing.  The image is unchanged: wave w of the group that owns
+// a phase plays the stored waves w % 4 and w % 4 + 4 of the unit -- their 2 x 8 wave-loads with the voff of each, their tiles, per tile the
+// k-blocks in cl_consume's order -- so every sum is the one the eight-wave schedule formed.  Ring: 2 slots x 16 wave-loads per wave.
+//   G0  slot 0: A0 -> C -> next A0      slot 1: A1 -> E -> next A1          G1  slot 0: B -> F0      slot 1: D -> F1
+//   X1 published: B (G1) | X1 swept: C (G0) | phase B: E (G0) | X2 published: D (G1) | X2 swept: F0 (G1) | phase D: next A0 (G0) |
+//   phase E + ffn epilogue: F1 in halves (G1) | phase F: next A1 (G0; the skip half, wanted in skip layers only)
+// Nothing is requested ahead of a publish (phases A and C end in granule stores), every slot is requested only after its unit was consumed,
+// and but for B and A1 -- their slots hold F0 / E until late, and phase A may not request -- every unit is at least a phase ahead.
+// The barrier that ends a phase waits for the requesting group too: 64 wave-loads are 1 k cycles of the address path, a whole unit per phase
+// fits B, D and F but not E.  Stamps of this schedule and of the one before: profiles/cluster_wave_groups.txt.
+// The epilogue wave requests nothing between a publish and the end of its sweep: its polls stand behind no load of its own.
+template <typename WT, int C, bool Q> struct ClGrp { static constexpr bool ON = C == 8 && WT::MFMA && !Q; };
+struct ClSchedGrp { static constexpr bool WIN = true; static constexpr int PRO = 0; typedef ClSeq<> W1A, W1B, W2A, W2B, WXA, WXB, W3, AF; };   // (the windows and their flags stay; what goes out in them is listed above)
+struct ClRing2 { u32x4 r[2][2][8]; };              // [slot][stored wave w % 4 | w % 4 + 4][wave-load]
+// unit at byte offset soff -> slot SLOT; voff: of stored wave w % 4.  on[h] false: stored wave h's loads are not wanted (stage A: the skip half and the y
+// waves only where the layer has a skip linear).  They are then requested past the end of the image -- the buffer's range check answers with zeros and
+// reads no memory -- instead of branched around: a slot written on one path only is kept twice and copied at the join, and the wait counts of every
+// unit requested before it are then those of the path WITH the loads behind them, i.e. vmcnt(0).  H: which of the two stored waves this call requests.
+#define DCLG_NOWHERE 0x7fff0000u
+template <int SLOT, int H = 3>
+__device__ __forceinline__ void clg_issue(ClRing2& ring, unsigned voff, __amdgpu_buffer_rsrc_t rsrc, unsigned soff, bool on0, bool on1) {
+    if constexpr (H & 1) {
+        const unsigned v0 = on0 ? voff : DCLG_NOWHERE;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ring.r[SLOT][0][i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, v0, soff + (unsigned)(i * 1024), 0);
+    }
+    if constexpr (H & 2) {
+        const unsigned v1 = on1 ? voff + 4u * 8u * 1024u : DCLG_NOWHERE;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ring.r[SLOT][1][i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, v1, soff + (unsigned)(i * 1024), 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
+// consume a slot: cl_consume's stage loads (k-block j / TPW, tile j % TPW) for both stored waves, alternating -- two independent accumulator
+// chains per tile index, one fragment read for both; per tile the k-blocks in cl_consume's order
+template <typename WT, int TPW, int J0, int KBOFF>
+__device__ __forceinline__ void clg_consume(const u32x4 (&slot)[2][8], const ClX& x, f32x4 (&acc)[2][TPW]) {
+    static_assert(WT::MFMA, "16-bit images only");
+    uint4 a4 = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int j = J0 + i, kb = j / TPW - KBOFF, t = j % TPW;
+        if (i == 0 || t == 0) a4 = *reinterpret_cast<const uint4*>(x.base + x.foff + kb * x.kbs);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            if constexpr (WT::HALF) acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, a4), __builtin_bit_cast(h16x8, slot[h][i]), acc[h][t], 0, 0, 0);
+            else acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a4), __builtin_bit_cast(bf16x8, slot[h][i]), acc[h][t], 0, 0, 0);
+        }
+    }
+}
+// value of the lane's tile: 16-lane group g of a wave writes tile g of acc[stored wave][tile]
+template <typename WT, int TPW>
+__device__ __forceinline__ float clg_out(const f32x4 (&acc)[2][TPW], int lane) {
+    const int h = TPW == 2 ? lane >> 5 : lane >> 4, t = TPW == 2 ? (lane >> 4) & 1 : 0;
+    float v = cl_out<WT>(acc[0][0]);
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+        for (int tt = 0; tt < TPW; ++tt) v = (h == hh && t == tt) ? cl_out<WT>(acc[hh][tt]) : v;
+    return v;
 }
 
 // ---- granules
@@ -375,7 +445,8 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
     // re-fills left until after the exchange: the last RU units of stage A (x half + skip half) and of stage C
     constexpr int A_DEF0 = cl_clamp(2 * G::TA - W::RU, 0, 2 * G::TA);          // first deferred unit of the 2 TA units of stage A
     constexpr int A_INL0 = cl_clamp(A_DEF0, 0, G::TA), A_INL1 = cl_clamp(A_DEF0 - G::TA, 0, G::TA), C_INL = cl_clamp(G::TB - W::RU, 0, G::TB);
-    typedef ClSched<C, WT::MFMA, Q> SCH;
+    constexpr bool GRP = ClGrp<WT, C, Q>::ON;   // two wave groups: see ClGrp
+    typedef std::conditional_t<GRP, ClSchedGrp, ClSched<C, WT::MFMA, Q>> SCH;
     constexpr bool WIN = SCH::WIN;       // (then stages A .. E request nothing inline: the windows do)
     const SeemeSampleArgs& A = ka.s;
     const DenLayout* __restrict__ lay = &ka.lay;
@@ -414,6 +485,8 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
     unsigned long long* const xg = ka.xg + (size_t)b * G::G_TOTAL;
     const __amdgpu_buffer_rsrc_t xr_ = __builtin_amdgcn_make_buffer_rsrc(xg, 0, G::G_TOTAL * 8, 0x00020000);
     const unsigned voff = (unsigned)wave * (unsigned)(W::UL * 1024) + (unsigned)lane * 16u;
+    const int w4 = wave & 3;                     // (GRP) the stored waves this wave plays: w4, w4 + 4
+    const unsigned gvoff = (unsigned)w4 * (unsigned)(W::UL * 1024) + (unsigned)lane * 16u;
     const int col = lane & 15;
     const ClX xa = cl_xin<WT>(XA, lane), xb = cl_xin<WT>(XB, lane), xh = cl_xin<WT>(XH, lane);
     const float sa_scale = 1.f / 16.f;           // one head of 256 dims
@@ -459,7 +532,14 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
         st4(RES + 4 * lane, xr);
     }
     ClRing<WT> ring;
-    {
+    ClRing2 gr;                                  // (GRP)
+    (void)gr; (void)gvoff; (void)w4;
+    if constexpr (GRP) {
+        if (wave < 4) {       // layer 0 has no skip linear; A1 is requested all the same (nowhere), as after every phase F: one count of loads in flight at a layer's start
+            clg_issue<0>(gr, gvoff, wg, (unsigned)(c * G::NU + G::U_A) * W::UNIT_BYTES, true, w4 < 2);
+            clg_issue<1>(gr, gvoff, wg, (unsigned)(c * G::NU + G::U_AS) * W::UNIT_BYTES, false, false);
+        }
+    } else {
         const unsigned b0 = (unsigned)((0 * C + c) * G::NU) * W::UNIT_BYTES;
         cl_issue<WT, C, Q, 0>(ring, wave, voff, wg, b0, b0, false, false);
         cl_issue<WT, C, Q, 1>(ring, wave, voff, wg, b0, b0, false, false);
@@ -511,8 +591,92 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
             const unsigned e1 = 1u + (unsigned)G::EPL * (unsigned)(step * SEEME_DEN_NL + l), e2 = e1 + 1u, e3 = e1 + 2u;   // epochs of this layer's exchanges
             (void)e3;
 
+            if constexpr (GRP) {
+                if (wave >= 4) {
+                    // ======== group G1: phases B, D, F; the same barriers as G0 below, which runs A, C, E and the epilogue wave's parts ========
+                    __syncthreads();                                                   // A
+                    {   // X1 published: the next layer's changing row (oldest load, see ClRow), then unit B
+                        ClRow nrow;
+                        cl_flag_wait(FLG + 1, e1);
+                        nrow.load(wave, lane, tt_next, A.catab + (((size_t)b * ca_R + ca_next) * SEEME_DEN_NL + ln) * 256, ln);
+                        __builtin_amdgcn_sched_barrier(0);
+                        clg_issue<0>(gr, gvoff, wg, bc + (unsigned)G::U_B * W::UNIT_BYTES, true, true);
+                        nrow.store(wave, lane, ROWS + (cur ^ 1) * R::ROWS);
+                    }
+                    __syncthreads();                                                   // X1
+                    {   // B: linear1 + ReLU
+                        f32x4 acc[2][1];
+                        cl_zero<1>(acc[0]); cl_zero<1>(acc[1]);
+                        clg_consume<WT, 1, 0, 0>(gr.r[0], xb, acc);
+                        cl_pin<1>(acc[0]); cl_pin<1>(acc[1]);
+                        if (lane < 32) {
+                            const int j = (w4 + 4 * (lane >> 4)) * 16 + col;
+                            cl_put1<WT>(XH, j, fmaxf(clg_out<WT, 1>(acc, lane) + v_l1b[j], 0.f));
+                        }
+                    }
+                    __syncthreads();                                                   // B
+                    cl_flag_wait(FLG + 1, e2);                                         // X2 published: D
+                    clg_issue<1>(gr, gvoff, wg, bc + (unsigned)G::U_D * W::UNIT_BYTES, true, true);
+                    cl_flag_wait(FLG + 2, e2);                                         // X2 swept: F0
+                    clg_issue<0>(gr, gvoff, wg, bc + (unsigned)G::U_F * W::UNIT_BYTES, true, true);
+                    __syncthreads();                                                   // C + X2
+                    {   // D: ffn.linear1 + GELU
+                        f32x4 acc[2][1];
+                        cl_zero<1>(acc[0]); cl_zero<1>(acc[1]);
+                        clg_consume<WT, 1, 0, 0>(gr.r[1], xa, acc);
+                        cl_pin<1>(acc[0]); cl_pin<1>(acc[1]);
+                        if (lane < 32) {
+                            const int j = (w4 + 4 * (lane >> 4)) * 16 + col;
+                            cl_put1<WT>(XH, j, fast_gelu(clg_out<WT, 1>(acc, lane) + v_f1b[j]));
+                        }
+                    }
+                    __syncthreads();                                                   // D
+                    // F1 in two halves, phase E and the ffn epilogue: the 64 wave-loads of a whole unit take the address path longer than phase E lasts,
+                    // and the barrier that ends a phase waits for the requesting group as well
+                    clg_issue<1, 1>(gr, gvoff, wg, bc + (unsigned)(G::U_F + 1) * W::UNIT_BYTES, true, true);
+                    __syncthreads();                                                   // E
+                    clg_issue<1, 2>(gr, gvoff, wg, bc + (unsigned)(G::U_F + 1) * W::UNIT_BYTES, true, true);
+                    __syncthreads();                                                   // ffn epilogue
+                    {   // F: ffn.proj_out.out_layers + residual; writes the next layer's input
+                        f32x4 acc[2][2];
+                        cl_zero<2>(acc[0]); cl_zero<2>(acc[1]);
+                        clg_consume<WT, 2, 0, 0>(gr.r[0], xb, acc);
+                        cl_pin<2>(acc[0]); cl_pin<2>(acc[1]);
+                        clg_consume<WT, 2, W::UL, 0>(gr.r[1], xb, acc);
+                        cl_pin<2>(acc[0]); cl_pin<2>(acc[1]);
+                        const int n = (2 * (w4 + 4 * (lane >> 5)) + ((lane >> 4) & 1)) * 16 + col;
+                        const float xn = RES[n] + clg_out<WT, 2>(acc, lane) + v_fo_b[n];
+                        RES[n] = xn;
+                        cl_put1<WT>(XA, n, xn);
+                        if (l < 2) cl_put1<WT>(SKF + 512 * l, n, xn);
+                    }
+                    __syncthreads();                                                   // F
+                    if (l + 1 == SEEME_DEN_NL) __syncthreads();                        // stack norm, scheduler step
+                    cur ^= 1;
+                    continue;
+                }
+            }
+
             // ================= A: in_proj' (+ folded skip linear), column-split by dims =================
-            {
+            if constexpr (GRP) {
+                f32x4 acc[2][1];
+                cl_zero<1>(acc[0]); cl_zero<1>(acc[1]);
+                clg_consume<WT, 1, 0, 0>(gr.r[0], xa, acc);
+                cl_pin<1>(acc[0]); cl_pin<1>(acc[1]);
+                if (skip) {   // second k-half: the skip input (see below)
+                    const ClX xs = cl_xin<WT>(SKF + (l == 3 ? 512 : 0), lane);
+                    clg_consume<WT, 1, W::UL, W::UL>(gr.r[1], xs, acc);
+                }
+                cl_pin<1>(acc[0]); cl_pin<1>(acc[1]);
+                if (lane < 32) {
+                    const int sw = w4 + 4 * (lane >> 4), d = (sw & 1) * 16 + col;      // stored wave = tile; waves 0,1: q; 2,3: k; 4,5: v'; 6,7: y
+                    const float val = clg_out<WT, 1>(acc, lane);
+                    if (sw < 2) QS[d] = val + v_in_b[d];
+                    else if (sw < 4) KS[d] = val + v_in_b[IN_ST + d];
+                    else if (sw < 6) cl_store_granule(xg + G::G_X1 + c * G::X1_G + d, e1, val + v_in_b[2 * IN_ST + d], local);
+                    else if (skip) cl_store_granule(xg + G::G_X1 + c * G::X1_G + G::S + d, e1, val + v_skip_b[d], local);
+                }
+            } else {
                 f32x4 acc[G::TA];
                 cl_zero<G::TA>(acc);
                 const bool act = skip || !ywave;
@@ -591,6 +755,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
                 }
                 if constexpr (WIN) {
                     cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W1B{});
+                    if constexpr (GRP) clg_issue<0>(gr, gvoff, wg, bc + (unsigned)G::U_C * W::UNIT_BYTES, true, true);
                     if (lane == 0) cl_flag_set(FLG + 2, e1);
                 }
                 DEN_DBG(0);
@@ -632,6 +797,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
                     cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W1A{});
                     cl_flag_wait(FLG + 2, e1);
                     cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W1B{});
+                    if constexpr (GRP) clg_issue<0>(gr, gvoff, wg, bc + (unsigned)G::U_C * W::UNIT_BYTES, true, true);
                 }
                 if constexpr (RSD) nrow.store(wave, lane, ROWS + (cur ^ 1) * R::ROWS);
             }
@@ -642,7 +808,9 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
             //  of the phase -- BEFORE the deferred re-fills: vmcnt is in order, and the store must not wait for them)
             if constexpr (Q) nxt.load(0, wave, lane, vp, Ln, tt_next, ln, A, b, c, ca_next, ca_R);
             if constexpr (!WIN) cl_refills<WT, C, Q, G::U_A + A_DEF0>(ring, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, 2 * G::TA - A_DEF0>{});   // slots of stage A
-            {
+            if constexpr (GRP) {      // (G1 computes; this group requests E)
+                clg_issue<1>(gr, gvoff, wg, bc + (unsigned)G::U_E * W::UNIT_BYTES, true, true);
+            } else {
                 f32x4 acc[G::TB];
                 cl_zero<G::TB>(acc);
                 cl_units<WT, C, Q, G::U_B, G::TB, G::TB, 0, 0, (WIN ? 0 : G::TB)>(ring, xb, acc, true, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, G::TB>{});
@@ -659,7 +827,13 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
 
             // ================= C: linear2, row-split -> X2 =================
             if constexpr (Q) nxt.load(1, wave, lane, vp, Ln, tt_next, ln, A, b, c, ca_next, ca_R);
-            {
+            if constexpr (GRP) {
+                f32x4 acc[2][2];
+                cl_zero<2>(acc[0]); cl_zero<2>(acc[1]);
+                clg_consume<WT, 2, 0, 0>(gr.r[0], xh, acc);
+                cl_pin<2>(acc[0]); cl_pin<2>(acc[1]);
+                cl_store_granule(xg + G::G_X2 + c * 256 + (2 * (w4 + 4 * (lane >> 5)) + ((lane >> 4) & 1)) * 16 + col, e2, clg_out<WT, 2>(acc, lane), local);
+            } else {
                 f32x4 acc[2];
                 cl_zero<2>(acc);
                 cl_units<WT, C, Q, G::U_C, G::TB, 2, 0, 0, C_INL>(ring, xh, acc, true, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, G::TB>{});
@@ -846,7 +1020,9 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
             // ================= D: ffn.linear1 + GELU (replicated) =================
             if constexpr (Q) nxt.load(3, wave, lane, vp, Ln, tt_next, ln, A, b, c, ca_next, ca_R);
             if constexpr (!Q && !WIN) cl_refills<WT, C, Q, G::U_C + C_INL>(ring, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, G::TB - C_INL>{});       // slots of stage C
-            {
+            if constexpr (GRP) {      // (G1 computes; this group requests the next layer's A0)
+                clg_issue<0>(gr, gvoff, wg, bn + (unsigned)G::U_A * W::UNIT_BYTES, true, nskip || w4 < 2);
+            } else {
                 f32x4 acc[1];
                 cl_zero<1>(acc);
                 cl_units<WT, C, Q, G::U_D, 1, 1, 0, 0, (WIN ? 0 : 1)>(ring, xa, acc, true, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, 1>{});
@@ -858,7 +1034,13 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
             if constexpr (Q) nxt.store(lane, STG + (cur ^ 1) * stg_sz);
             __syncthreads(); DEN_DBG(0);
             // ================= E: ffn.linear2 -> LayerNorm, AdaLN, SiLU (replicated) =================
-            {
+            if constexpr (GRP) {
+                f32x4 acc[2][2];
+                cl_zero<2>(acc[0]); cl_zero<2>(acc[1]);
+                clg_consume<WT, 2, 0, 0>(gr.r[1], xh, acc);
+                cl_pin<2>(acc[0]); cl_pin<2>(acc[1]);
+                PART[(2 * (w4 + 4 * (lane >> 5)) + ((lane >> 4) & 1)) * 16 + col] = clg_out<WT, 2>(acc, lane);
+            } else {
                 f32x4 acc[2];
                 cl_zero<2>(acc);
                 cl_units<WT, C, Q, G::U_E, 1, 2, 0, 0, (WIN ? 0 : 1)>(ring, xh, acc, true, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, 1>{});
@@ -881,7 +1063,10 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
             // ================= F: ffn.proj_out.out_layers + residual (replicated); writes the next layer's input =================
             if constexpr (Q) nxt.load(4, wave, lane, vp, Ln, tt_next, ln, A, b, c, ca_next, ca_R);
             if constexpr (WIN) __builtin_amdgcn_sched_barrier(0);   // (the fence of a window that requests nothing any more; without it stage F's first fragment reads move up)
-            {
+            if constexpr (GRP) {      // (G1 computes; this group requests the next layer's A1, the skip half -- ONE request site for all four waves:
+                                      //  requested in the ffn-epilogue window, before / behind the release, the slot is kept twice and copied)
+                clg_issue<1>(gr, gvoff, wg, bn + (unsigned)G::U_AS * W::UNIT_BYTES, nskip, nskip);
+            } else {
                 f32x4 acc[2];
                 cl_zero<2>(acc);
                 cl_units<WT, C, Q, G::U_F, 2, 2, 0, 0, (WIN ? 0 : 2)>(ring, xb, acc, true, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, 2>{});
@@ -937,8 +1122,13 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
     }
     DEN_DBG(3);
     if (epi && c == 0) st4(A.out + (size_t)b * 256 + 4 * lane, ld4(KEEP + 4 * lane));
+    if constexpr (GRP) {
 #pragma unroll
-    for (int s = 0; s < W::RU; ++s) asm volatile("" ::"v"(ring.r[s][0].x));
+        for (int s = 0; s < 2; ++s) asm volatile("" ::"v"(gr.r[s][0][0].x));
+    } else {
+#pragma unroll
+        for (int s = 0; s < W::RU; ++s) asm volatile("" ::"v"(ring.r[s][0].x));
+    }
 }
 
 template <int C>

@@ -401,10 +401,10 @@ class MldDenoiser(nn.Module):
         want = os.environ.get("SEEME_DEN_CLUSTER")
         want = self.cluster if want is None else (want if want == "auto" else int(want))
         ms = os.environ.get("SEEME_DEN_CLUSTER_MS", "1") != "0" and self.cluster_ms
-        if (want != "auto" or not ms or B <= 32 or N not in (1, 2) or cfg or per_sample or self.num_heads != 1
+        forced = os.environ.get("SEEME_DEN_CLUSTER_MS_PLAN")           # "C,samples" (samples >= 2): measurement and tests only, any B
+        if (want != "auto" or not ms or (B <= 32 and not forced) or N not in (1, 2) or cfg or per_sample or self.num_heads != 1
                 or self.weight_dtype not in ("fp16", "bf16")):
             return Cc, 1
-        forced = os.environ.get("SEEME_DEN_CLUSTER_MS_PLAN")           # "C,samples" (samples >= 2): measurement only
         if forced:
             C4, spc = (int(x) for x in forced.split(","))
             return C4, spc
