@@ -1310,11 +1310,19 @@ static int skip_lin_h(hipStream_t st, const float* a1, const float* a2, const ui
     return launch_linear_h(ha, st);
 }
 
+// Below 8 tokens V^T [B][256][spv] (spv = 32 > 4 S) is larger than the R x 1024 halves behind q | k: in the decoder it ran on into
+// cvec, whose floats then stood in the value granules (NaN as fp16) and were themselves overwritten by the next layer's V.  The
+// packed-key region, which only k_layer_h uses, holds at least B x 16 x 512 halves = B x 256 x 32: V^T goes there.
+static void place_vt_unfused(WsH& ws, int S_carved) {
+    if (ws.spv > 4 * S_carved) ws.vt = reinterpret_cast<unsigned short*>(ws.kp[0]);
+}
+
 static int vae_encode_h16_unfused(const SeemeVaeWeights* w, const float* features, const int32_t* lengths, int B, int T, float* mu,
                          void* workspace, hipStream_t st) {
     const SeemeVaeWeightsH* H = w->h16;
     const int S = T + 2, F = w->nfeats;
     WsH ws = carve_h(workspace, B, S);
+    place_vt_unfused(ws, S);
     const SeemeSkipStack& E = w->enc;
     SEEME_HIP(hipMemsetAsync(ws.vt, 0, (size_t)B * 256 * ws.spv * 2, st));
     hipLaunchKernelGGL(k_enc_tokens_h, dim3((B * 512 + 255) / 256), dim3(256), 0, st, w->token, w->pe_enc, ws.x, B, S);
@@ -1343,6 +1351,7 @@ static int vae_decode_h16_unfused(const SeemeVaeWeights* w, const float* z, cons
     const int S = T, F = w->nfeats;
     WsH ws = carve_h(workspace, B, S + 2);
     ws.spv = (S + 31) & ~31;
+    place_vt_unfused(ws, S + 2);
     const SeemeSkipStack& Dk = w->dec;
     int rc;
     SEEME_HIP(hipMemsetAsync(ws.vt, 0, (size_t)B * 256 * ws.spv * 2, st));

@@ -724,7 +724,8 @@ def test_pointnet_bf16_one_point_equals_its_copies(dev):
 
 def test_vae_fp16_mfma_mode(dev):
     """Throughput mode of the VAE (fp16 MFMA operands, fp32 accumulation and residual stream): measured against the
-    reference fixtures; bound 2e-2 of the output range (reported, not the 1e-4 parity gate)."""
+    reference fixtures; bound 2.17e-3 of the output range = 3 x the worst measured figure, 7.24e-4 (not the 1e-4 parity gate).
+    The index edges of this path are held by tests/test_gpu_vae_edges.py."""
     from seeme_amd.mld_vae import MldVae
     for name, F in (("vae_F132_T24.npz", 132), ("vae_F75_T60.npz", 75), ("vae_F132_T196.npz", 132)):
         g = load_golden(name)
@@ -735,7 +736,7 @@ def test_vae_fp16_mfma_mode(dev):
         dec = vae.decode(torch.from_numpy(g["mu"]).to(dev), lengths)
         e_dec = rel_err(dec.cpu().numpy(), g["decoded"])
         print(f"fp16-MFMA VAE {name}: mu rel err {e_mu:.3e}, decode rel err {e_dec:.3e}")
-        assert e_mu < 2e-2 and e_dec < 2e-2
+        assert e_mu < 2.17e-3 and e_dec < 2.17e-3
 
 
 def test_vae_long_ragged_sequences_fp16_vs_fp32_vs_oracle(dev):
@@ -758,9 +759,10 @@ def test_vae_long_ragged_sequences_fp16_vs_fp32_vs_oracle(dev):
     vae.precision = "fp16"
     _, d16 = vae.encode(torch.from_numpy(x).to(dev), None, lengths)
     dec16 = vae.decode(d32.loc, lengths)
-    assert rel_err(d16.loc.cpu().numpy(), d32.loc.cpu().numpy()) < 2e-2
-    for b, Lb in enumerate(lengths):
-        assert rel_err(dec16[b, :Lb].cpu().numpy(), dec32[b, :Lb].cpu().numpy()) < 2e-2
+    e_mu = rel_err(d16.loc.cpu().numpy(), d32.loc.cpu().numpy())
+    e_dec = [rel_err(dec16[b, :Lb].cpu().numpy(), dec32[b, :Lb].cpu().numpy()) for b, Lb in enumerate(lengths)]
+    print(f"fp16-MFMA VAE T=300 ragged vs fp32 path: mu rel err {e_mu:.3e}, decode rel err per sequence {e_dec}")
+    assert e_mu < 1.65e-3 and max(e_dec) < 2.6e-3             # 3 x the measured 5.51e-4 and 8.70e-4
 
 
 def test_vae_fp16_large_batch_matches_small_batch(dev):
@@ -779,7 +781,9 @@ def test_vae_fp16_large_batch_matches_small_batch(dev):
     assert torch.equal(big[:, idx], small)
     vae.precision = "fp32"
     ref = vae.encode_dist(x[idx].contiguous(), [T] * len(idx))
-    assert rel_err(small.cpu().numpy(), ref.cpu().numpy()) < 2e-2
+    e = rel_err(small.cpu().numpy(), ref.cpu().numpy())
+    print(f"fp16-MFMA VAE B=176 rows vs fp32 path: [mu, logvar] rel err {e:.3e}")
+    assert e < 1.39e-3                                         # 3 x the measured 4.64e-4
 
 
 # ----------------------------------------------------------------------------- train.py / test.py equivalents
