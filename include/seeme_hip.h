@@ -39,7 +39,11 @@ const char* seeme_last_error(void);
  * Replaces torch.nn.functional.linear (+ fused neighbours) wherever the path uses it, e.g.
  * skel_embedding mld_vae.py:147, final_layer :251, skip Linear(2D,D) cross_attention.py:58-60
  * (A | A2 concatenation without materialising it), ResnetBlockFC respointnet.py:88-97.
- * K may be any size: W rows must be readable for roundup16(K) floats (zero padded) -- ldw says so. */
+ * K may be any size up to SEEME_LINEAR_MAX_K (a 32-row tile of A, padded to roundup16(K), shares a workgroup's 163,840 B
+ * of LDS with the output tile; a larger K is refused): W rows must be readable for roundup16(K) floats (zero padded)
+ * -- ldw says so -- and ldw must be a multiple of 4 with W 16-byte aligned.  A, A2, res and Y may have any 4-byte
+ * alignment and any row stride >= their width; 16-byte aligned rows take the vector paths. */
+#define SEEME_LINEAR_MAX_K 1008
 typedef struct {
     const float* A;  int lda;         /* [M, K1] */
     const float* A2; int lda2;        /* optional [M, K-K1] (concat along K); NULL if unused */
@@ -47,7 +51,7 @@ typedef struct {
     const float* W;  int ldw;         /* [N, >=roundup16(K)] */
     const float* bias;                /* [N] or NULL */
     const float* res; int ldr;        /* optional residual [M,N] added after act */
-    const float* ln_w; const float* ln_b;          /* optional LayerNorm over N (N must be <= 256) */
+    const float* ln_w; const float* ln_b;          /* optional LayerNorm over N (needs N == 256) */
     const float* pre_ln_w; const float* pre_ln_b;  /* optional LayerNorm over K applied to A rows first */
     float* Y; int ldy;
     int M, N, K;

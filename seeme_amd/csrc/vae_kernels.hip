@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void k_linear(const LinearKArgs ka) {
     __syncthreads();
 
     // ---- row pass: residual, LayerNorm, coalesced store.  wave w -> rows 8w..8w+7, lane -> 4 cols
-    const bool vec_ok = ((a.ldy & 3) == 0) && ((a.N & 3) == 0);
+    const bool vec_ok = ((a.ldy & 3) == 0) && ((a.N & 3) == 0) && ((reinterpret_cast<size_t>(a.Y) & 15) == 0);
     // residual rows as float4, all 8 of the wave requested together (when rows are 16-byte aligned and whole); LayerNorm
     // parameters once per phase
     const bool res_vec = a.res != nullptr && ((a.ldr & 3) == 0) && ((a.N & 3) == 0) && ((reinterpret_cast<size_t>(a.res) & 15) == 0);
@@ -158,6 +158,7 @@ __global__ __launch_bounds__(256) void k_linear(const LinearKArgs ka) {
     }
 }
 
+#define SEEME_LDS_PER_WORKGROUP 163840   // bytes of LDS one workgroup may have on gfx950 (160 KiB per CU)
 #ifndef SEEME_NARROW_MIN_N
 #define SEEME_NARROW_MIN_N 512
 #endif
@@ -172,8 +173,10 @@ int seeme_launch_linear(const LinearKArgs& ka, hipStream_t st) {
     const int Kp = (a.K + 15) & ~15;
     if (a.ldw < Kp) return seeme_fail("seeme_linear: ldw < roundup16(K) (weights must be zero padded)");
     if ((a.ldw & 3) != 0) return seeme_fail("seeme_linear: ldw must be a multiple of 4");
-    if (Kp > 1024) return seeme_fail("seeme_linear: K > 1024 not supported");
-    const size_t lds = (size_t)(TILE_M * (Kp + LDS_PAD) + TILE_M * (CH_N + LDS_PAD)) * sizeof(float);
+    // the A tile [32][Kp+8] and the output tile [32][264] share one workgroup's LDS: Kp = 1008 needs all 163,840 B of it
+    const size_t lds = (size_t)(TILE_M * ((size_t)Kp + LDS_PAD) + TILE_M * (CH_N + LDS_PAD)) * sizeof(float);
+    static_assert(SEEME_LINEAR_MAX_K == (SEEME_LDS_PER_WORKGROUP / (TILE_M * sizeof(float)) - (CH_N + 2 * LDS_PAD)) / 16 * 16, "header's K limit");
+    if (lds > SEEME_LDS_PER_WORKGROUP) return seeme_fail("seeme_linear: K > 1008 not supported (A tile + output tile exceed the 163840 B of LDS a workgroup may have)");
     LinearKArgs k2 = ka;
     const long wide = (long)((a.M + TILE_M - 1) / TILE_M) * ((a.N + CH_N - 1) / CH_N) * (ka.nz > 1 ? ka.nz : 1);
     k2.narrow = (a.ln_w == nullptr && a.N >= SEEME_NARROW_MIN_N && wide <= SEEME_NARROW_MAX) ? 1 : 0;     // too few 256-column workgroups to fill 256 CUs
