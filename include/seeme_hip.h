@@ -90,6 +90,9 @@ typedef struct {
     SeemeXfLayerH enc[SEEME_NLAYERS], dec[SEEME_NLAYERS];
     const uint16_t *enc_skip[2], *dec_skip[2];
     const uint16_t *emb_w, *fin_w, *ca_fold_w;
+    /* the decoder's sample-independent prologue (seeme_vae_dec_prologue_h16), built for dec_pro_T frames; NULL: none.  Decode reads
+     * it only when dec_pro_T equals its own T, and never writes it. */
+    const void* dec_pro; int dec_pro_T;
 } SeemeVaeWeightsH;
 
 typedef struct {
@@ -122,6 +125,13 @@ int seeme_vae_encode(const SeemeVaeWeights* w, const float* features, const int3
  * (padded frames not zeroed, as in the reference :253). */
 int seeme_vae_decode(const SeemeVaeWeights* w, const float* z, const int32_t* lengths,
                      int B, int T, float* feats, void* workspace, size_t ws_bytes, void* stream);
+
+/* The fp16 decoder's first-layer inputs for T frames.  The queries are zeros + learned positional rows, so the rows and their
+ * q | K | V^T depend on the weights and on T only: built once into buf (16-byte aligned, seeme_vae_dec_prologue_bytes(T) bytes; x rows
+ * [T][256] fp32, q [T][256] fp16, K and V^T fragment-packed for ONE sequence) and handed to decode through SeemeVaeWeightsH.dec_pro.
+ * Rebuild it whenever the weights change. */
+size_t seeme_vae_dec_prologue_bytes(int T);
+int seeme_vae_dec_prologue_h16(const SeemeVaeWeights* w, int T, void* buf, size_t bytes, void* stream);
 
 /* ------------------------------------------------------------------ denoiser + sampling loop
  * mld.models.architectures.mld_denoiser.MldDenoiser (arch trans_enc, MD_TRANS layers

@@ -28,5 +28,8 @@ if k == 5:
     t2 = np.array(buf[16:21], dtype=np.float64)
     print("  LN1 phase detail (cycles since the phase's barrier):", [int(x - t[5]) for x in t2],
           "= loads issued, tile + residual in registers, LN of 8 rows done, 2nd LN done, operand rows stored")
+    if buf[21] and buf[22]:
+        print("  cross vector formed in the layer (cycles):", int(buf[21] - t[2]), "= its eight k-blocks requested, ahead of the softmax;",
+              int(buf[22] - t[3]), "= MFMAs + bias -> LDS, ahead of P V")
     t3 = np.array(buf[23:26], dtype=np.float64)
     print("  out_proj phase detail (cycles since the phase's barrier):", [int(x - t[4]) for x in t3], "= GEMM done, tile stored, FFN requests issued; the rest is the barrier")

@@ -51,7 +51,7 @@ class XfLayerH(C.Structure):
 
 class VaeWeightsH(C.Structure):
     _fields_ = [("enc", XfLayerH * NLAYERS), ("dec", XfLayerH * NLAYERS), ("enc_skip", fp * 2), ("dec_skip", fp * 2),
-                ("emb_w", fp), ("fin_w", fp), ("ca_fold_w", fp)]
+                ("emb_w", fp), ("fin_w", fp), ("ca_fold_w", fp), ("dec_pro", fp), ("dec_pro_T", C.c_int)]
 
 
 def pack_mfma16(W, dtype):
@@ -188,6 +188,8 @@ _SIGNATURES = {
     "seeme_vae_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "seeme_vae_encode": (C.c_int, [C.POINTER(VaeWeights), fp, fp, C.c_int, C.c_int, fp, fp, fp, C.c_size_t, fp]),
     "seeme_vae_decode": (C.c_int, [C.POINTER(VaeWeights), fp, fp, C.c_int, C.c_int, fp, fp, C.c_size_t, fp]),
+    "seeme_vae_dec_prologue_bytes": (C.c_size_t, [C.c_int]),
+    "seeme_vae_dec_prologue_h16": (C.c_int, [C.POINTER(VaeWeights), C.c_int, fp, C.c_size_t, fp]),
     "seeme_denoiser_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "seeme_denoiser_time_tables": (C.c_int, [C.POINTER(DenoiserWeights), fp, C.c_int, fp, fp, C.c_size_t, fp]),
     "seeme_denoiser_cond_tables": (C.c_int, [C.POINTER(DenoiserWeights), fp, C.c_int, C.c_int, fp, fp, C.c_size_t, fp]),

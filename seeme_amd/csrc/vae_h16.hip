@@ -806,7 +806,13 @@ struct LayerHArgs {
     const uint4* skip_w; const float* skip_b; const float* skip_src; float* xnext;
     const uint4* qkv_w; const float* qkv_b; unsigned short* q_out; uint4* kp_out; uint4* vp_out;
     const uint4* proj_w; const float* proj_b; float* feats; int F;
+    // the decoder's cross-attention vector formed by the workgroup itself (layer_cvec_in instantiations; cvec is NULL then):
+    // c = ca_fold_w[256 layer .. +255] z[b] + ca_fold_b[...] from the packed matrix k_linear_h reads, the same MFMAs in the same order
+    const float* z; const uint4* cf_w; const float* cf_b; int layer;
 };
+// the instantiation that runs the launches of at most one workgroup per CU: there the vector's own launch costs more than 5 GEMVs per sample
+template <int WAVES, int RW>
+__host__ __device__ constexpr bool layer_cvec_in() { return WAVES == 8 && RW == 4; }
 
 __device__ __forceinline__ void rows_to_h16(unsigned short* Xh, int ldh, int row, int lane, float4 v) {
     const unsigned lo = (unsigned)f2h(v.x) | ((unsigned)f2h(v.y) << 16), hi = (unsigned)f2h(v.z) | ((unsigned)f2h(v.w) << 16);
@@ -941,6 +947,21 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? LAYER_WPE : 1) void k_laye
     const BiasRegs<NTL> bias_o = bias_load<NTL>(a.bo, wave * CW, 256);
     BRing<NTL, PFA> ring_o;
     prime_packed(ring_o, a.wo, 8, wave * NTL, 16, 8);
+    // cross-attention vector of this layer and sample (cv_in): z[b] is row 0 of a zeroed 16-row operand tile.  All eight k-blocks of the
+    // wave's n-tiles are requested when the softmax begins -- the one phase with no vector-memory traffic of its own -- and the MFMAs
+    // run when it ends.  (Requested at kernel start, half consumed before the softmax, measured the same within 0.2 us per layer:
+    // what a decoder layer pays, about 1 us, is 224 workgroups each pulling 128 KB more through L2, wherever the requests stand.)
+    const bool cv_in = layer_cvec_in<WAVES, RW>() && a.z != nullptr;
+    unsigned short* Zh = R1 + ROWS * ldq;
+    float* CVs = reinterpret_cast<float*>(Zh + 16 * ldq);
+    const int cv_t0 = 16 * a.layer + wave * NTL;
+    BRing<NTL, 8> ring_c;
+    BiasRegs<NTL> bias_c;
+    if (cv_in) {
+        bias_c = bias_load<NTL>(a.cf_b + 256 * a.layer, wave * CW, 256);
+        for (int i = tid; i < 15 * ldq / 8; i += NT) reinterpret_cast<uint4*>(Zh + ldq)[i] = make_uint4(0u, 0u, 0u, 0u);
+        if (wave == 0) rows_to_h16(Zh, ldq, 0, lane, *reinterpret_cast<const float4*>(a.z + (size_t)b * 256 + lane * 4));
+    }
     LAYER_DBG(0);
     {   // Q tile
         uint4 qv[4];
@@ -977,10 +998,22 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? LAYER_WPE : 1) void k_laye
     }
     __syncthreads();
     LAYER_DBG(2);
+    if (cv_in) prime_packed(ring_c, a.cf_w, 8, cv_t0, 16 * SEEME_NLAYERS, 8);
+    LAYER_DBG(21);
     if (a.Sp == 256) attn_softmax_rows<4, RW>(Ps, ldp, Ph, ldph, wave, lane);
     else attn_softmax_rows<8, RW>(Ps, ldp, Ph, ldph, wave, lane);
     __syncthreads();
     LAYER_DBG(3);
+    if (cv_in) {   // eight k-blocks in order, one accumulator per n-tile; + bias in fp32 as k_linear_h adds it; row 0 of the tile is the vector
+        f32x4 acc_c[1][NTL];
+        acc_zero(acc_c);
+        gemm_packed<1, NTL, 8>(Zh, ldq, a.cf_w, 8, cv_t0, 16 * SEEME_NLAYERS, 8, acc_c, ring_c);
+        if (kq == 0) {
+#pragma unroll
+            for (int nt = 0; nt < NTL; ++nt) CVs[wave * CW + nt * 16 + r] = acc_c[0][nt][0] + bias_c.v[nt];
+        }
+    }
+    LAYER_DBG(22);
     {   // O = P V
         f32x4 acc[MTL][NTL];
         acc_zero(acc);
@@ -1017,7 +1050,9 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? LAYER_WPE : 1) void k_laye
     {   // +residual, LN1 [, + cross-attention vector, LN]; rows stay in registers, fp16 copy is the FFN operand
         const LnParams lp = ln_params256_opt(a.n1_w, a.n1_b, a.n1_w), lc = ln_params256_opt(a.lnc_w, a.lnc_b, a.n1_w);
         float4 xr[RW];
-        const float4 cv = *reinterpret_cast<const float4*>((a.cvec != nullptr ? a.cvec + (size_t)b * a.cvec_ld : a.n1_w) + lane * 4);
+        const bool has_cv = cv_in || a.cvec != nullptr;
+        const float4 cv = cv_in ? *reinterpret_cast<const float4*>(CVs + lane * 4)
+                                : *reinterpret_cast<const float4*>((a.cvec != nullptr ? a.cvec + (size_t)b * a.cvec_ld : a.n1_w) + lane * 4);
 #pragma unroll
         for (int rr = 0; rr < RW; ++rr) {
             const int s = q0 + wave * RW + rr;
@@ -1033,7 +1068,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? LAYER_WPE : 1) void k_laye
         LAYER_DBG(17);
         wave_layernorm256_rows<RW>(x1, lp, a.eps);
         LAYER_DBG(18);
-        if (a.cvec != nullptr) {
+        if (has_cv) {
 #pragma unroll
             for (int rr = 0; rr < RW; ++rr) x1[rr] = make_float4(x1[rr].x + cv.x, x1[rr].y + cv.y, x1[rr].z + cv.z, x1[rr].w + cv.w);
             wave_layernorm256_rows<RW>(x1, lc, a.eps);
@@ -1158,22 +1193,33 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? LAYER_WPE : 1) void k_laye
 template <int WAVES, int RW>
 static int launch_layer_w(const LayerHArgs& a, hipStream_t st) {
     constexpr int ROWS = RW * WAVES;
-    const size_t lds = (size_t)ROWS * (a.Sp + LDS_PAD) * 4 + (size_t)ROWS * (256 + HPAD) * 2;
+    if (a.z != nullptr && !layer_cvec_in<WAVES, RW>()) return seeme_fail("layer_h: this instantiation does not form the cross-attention vector");
+    const size_t lds = (size_t)ROWS * (a.Sp + LDS_PAD) * 4 + (size_t)ROWS * (256 + HPAD) * 2 +
+                       (layer_cvec_in<WAVES, RW>() ? (size_t)16 * (256 + HPAD) * 2 + 256 * 4 : 0);
     dim3 grid((a.q_rows + ROWS - 1) / ROWS, a.B);
     SEEME_HIP(hipFuncSetAttribute((const void*)k_layer_h<WAVES, RW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((k_layer_h<WAVES, RW>), grid, dim3(64 * WAVES), lds, st, a);
     return seeme_check_launch("k_layer_h");
 }
+// 0: <4, 8>, 1: <8, 4>, 2: <8, 8>
+static int layer_form(int B, int q_rows, int S) {
+    static int rows = -1, w8_max = -1;
+    if (rows < 0) { const char* e = getenv("SEEME_LAYER_ROWS"); rows = e ? atoi(e) : 32; }
+    if (w8_max < 0) { const char* e = getenv("SEEME_LAYER_W8_MAX"); w8_max = e ? atoi(e) : 256; }
+    const int Sp = (S + CH_N - 1) / CH_N * CH_N;
+    if (rows == 64 && Sp <= 256 && q_rows > 32) return 2;
+    const long wgs = (long)B * ((q_rows + 31) / 32);
+    return wgs <= w8_max ? 1 : 0;
+}
+// whether a decoder layer of this shape forms its cross-attention vector itself (LayerHArgs.z) or reads it (LayerHArgs.cvec)
+static bool layer_forms_cvec(int B, int q_rows, int S) { return layer_form(B, q_rows, S) == 1; }
 static int launch_layer_h(const LayerHArgs& a_in, hipStream_t st) {
     LayerHArgs a = a_in;
     if (a.S <= 0 || a.S > 512) return seeme_fail("layer_h: S must be in 1..512");
     a.Sp = (a.S + CH_N - 1) / CH_N * CH_N;
-    static int rows = -1, w8_max = -1;
-    if (rows < 0) { const char* e = getenv("SEEME_LAYER_ROWS"); rows = e ? atoi(e) : 32; }
-    if (w8_max < 0) { const char* e = getenv("SEEME_LAYER_W8_MAX"); w8_max = e ? atoi(e) : 256; }
-    if (rows == 64 && a.Sp <= 256 && a.q_rows > 32) return launch_layer_w<8, 8>(a, st);
-    const long wgs = (long)a.B * ((a.q_rows + 31) / 32);
-    return wgs <= w8_max ? launch_layer_w<8, 4>(a, st) : launch_layer_w<4, 8>(a, st);
+    const int form = layer_form(a.B, a.q_rows, a.S);
+    if (form == 2) return launch_layer_w<8, 8>(a, st);
+    return form == 1 ? launch_layer_w<8, 4>(a, st) : launch_layer_w<4, 8>(a, st);
 }
 
 
@@ -1436,6 +1482,38 @@ int seeme_vae_encode_h16(const SeemeVaeWeights* w, const float* features, const 
     return launch_layer_h(a, st);
 }
 
+// The decoder's sample-independent prologue as a constant of (weights, T): ONE sequence's x rows, q and fragment-packed K | V^T,
+// each part 16-byte aligned (1024 T, 512 T, 8192 ceil(T/16) and 16384 ceil(T/32) bytes).
+struct DecPro { float* x; KvSet kv; };
+static DecPro carve_dec_pro(void* buf, int T) {
+    char* p = static_cast<char*>(buf);
+    DecPro d;
+    d.x = reinterpret_cast<float*>(p); p += (size_t)T * 256 * 4;
+    d.kv.q = reinterpret_cast<unsigned short*>(p); p += (size_t)T * 256 * 2;
+    d.kv.kp = reinterpret_cast<uint4*>(p); p += (size_t)((T + 15) >> 4) * 512 * 16;
+    d.kv.vp = reinterpret_cast<uint4*>(p);
+    return d;
+}
+extern "C" size_t seeme_vae_dec_prologue_bytes(int T) {
+    if (T < 1) return 0;
+    return (size_t)T * 256 * 6 + (size_t)((T + 15) >> 4) * 512 * 16 + (size_t)((T + 31) >> 5) * 16 * 64 * 16;
+}
+static int launch_dec_pro(const SeemeVaeWeights* w, int T, float* x, const KvSet& kv, hipStream_t st) {
+    ProHArgs p{};
+    // the decoder's first-layer rows and their q | K | V do not depend on the sample: ONE sequence's worth, read by every batch member
+    p.mode = 2; p.B = 1; p.S = T; p.T = T; p.F = w->nfeats; p.spv = (T + 31) & ~31; p.pe = w->pe_dec; p.x = x;
+    p.qkv_w = (const uint4*)w->h16->dec[0].in_w; p.qkv_b = w->dec.layer[0].in_b; p.q_out = kv.q; p.kp_out = kv.kp; p.vp_out = kv.vp;
+    return launch_pro_h(p, st);
+}
+extern "C" int seeme_vae_dec_prologue_h16(const SeemeVaeWeights* w, int T, void* buf, size_t bytes, void* stream) {
+    if (w == nullptr || w->h16 == nullptr) return seeme_fail("vae_dec_prologue: fp16 weight image missing");
+    if (T < 1 || T > 512) return seeme_fail("vae_dec_prologue: T must be in 1..512");
+    if (buf == nullptr || (reinterpret_cast<size_t>(buf) & 15) != 0) return seeme_fail("vae_dec_prologue: buffer must be 16-byte aligned");
+    if (bytes < seeme_vae_dec_prologue_bytes(T)) return seeme_fail("vae_dec_prologue: buffer too small");
+    const DecPro d = carve_dec_pro(buf, T);
+    return launch_dec_pro(w, T, d.x, d.kv, (hipStream_t)stream);
+}
+
 int seeme_vae_decode_h16(const SeemeVaeWeights* w, const float* z, const int32_t* lengths, int B, int T, float* feats,
                          void* workspace, hipStream_t st) {
     const SeemeVaeWeightsH* H = w->h16;
@@ -1448,28 +1526,35 @@ int seeme_vae_decode_h16(const SeemeVaeWeights* w, const float* z, const int32_t
     kv_sets(ws, B, kv);
     int rc;
     const int CL = SEEME_NLAYERS * 256;
-    if ((rc = lin_h(st, z, 256, H->ca_fold_w, 256, CL, w->ca_fold_b, ws.cvec, CL, B))) return rc;
-    {
-        ProHArgs p{};
-        // the decoder's first-layer rows and their q | K | V do not depend on the sample: ONE sequence's worth, read by every batch member
-        p.mode = 2; p.B = 1; p.S = S; p.T = T; p.F = F; p.spv = ws.spv; p.pe = w->pe_dec; p.x = ws.x;
-        p.qkv_w = (const uint4*)H->dec[0].in_w; p.qkv_b = Dk.layer[0].in_b; p.q_out = kv[0].q; p.kp_out = kv[0].kp; p.vp_out = kv[0].vp;
-        if ((rc = launch_pro_h(p, st))) return rc;
-    }
-    LayerHArgs a = layer_args(Dk.layer[0], H->dec[0], kv[0], ws.x, lengths, B, S, ws.spv, 0, S, ws.cvec + 0 * 256, CL);
+    // the cross-attention vectors: formed inside the 8-wave layer kernel, by a launch of their own for the larger grids
+    const bool cv_in = layer_forms_cvec(B, S, S);
+    if (!cv_in && (rc = lin_h(st, z, 256, H->ca_fold_w, 256, CL, w->ca_fold_b, ws.cvec, CL, B))) return rc;
+    auto dec_args = [&](int l, const KvSet& in, const float* res) {
+        LayerHArgs a = layer_args(Dk.layer[l], H->dec[l], in, res, lengths, B, S, ws.spv, 0, S, ws.cvec + l * 256, CL);   // decoder norms
+        if (cv_in) { a.cvec = nullptr; a.z = z; a.cf_w = (const uint4*)H->ca_fold_w; a.cf_b = w->ca_fold_b; a.layer = l; }
+        return a;
+    };
+    // layer 0's inputs: the cached prologue when it was built for this T (never written here), else one launch into set 0
+    KvSet in0 = kv[0];
+    const float* res0 = ws.x;
+    if (H->dec_pro != nullptr && H->dec_pro_T == T) {
+        const DecPro d = carve_dec_pro(const_cast<void*>(H->dec_pro), T);
+        in0 = d.kv; res0 = d.x;
+    } else if ((rc = launch_dec_pro(w, T, ws.x, kv[0], st))) return rc;
+    LayerHArgs a = dec_args(0, in0, res0);
     a.in_shared = 1;
     a.out = ws.sk0; tail_qkv(a, Dk.layer[1], H->dec[1], kv[1]);
     if ((rc = launch_layer_h(a, st))) return rc;
-    a = layer_args(Dk.layer[1], H->dec[1], kv[1], ws.sk0, lengths, B, S, ws.spv, 0, S, ws.cvec + 1 * 256, CL);
+    a = dec_args(1, kv[1], ws.sk0);
     a.out = ws.sk1; tail_qkv(a, Dk.layer[2], H->dec[2], kv[0]);
     if ((rc = launch_layer_h(a, st))) return rc;
-    a = layer_args(Dk.layer[2], H->dec[2], kv[0], ws.sk1, lengths, B, S, ws.spv, 0, S, ws.cvec + 2 * 256, CL);
+    a = dec_args(2, kv[0], ws.sk1);
     tail_skip(a, H->dec_skip[0], Dk.skip_b[0], ws.sk1, ws.x); tail_qkv(a, Dk.layer[3], H->dec[3], kv[1]);
     if ((rc = launch_layer_h(a, st))) return rc;
-    a = layer_args(Dk.layer[3], H->dec[3], kv[1], ws.x, lengths, B, S, ws.spv, 0, S, ws.cvec + 3 * 256, CL);
+    a = dec_args(3, kv[1], ws.x);
     tail_skip(a, H->dec_skip[1], Dk.skip_b[1], ws.sk0, ws.x); tail_qkv(a, Dk.layer[4], H->dec[4], kv[0]);
     if ((rc = launch_layer_h(a, st))) return rc;
-    a = layer_args(Dk.layer[4], H->dec[4], kv[0], ws.x, lengths, B, S, ws.spv, 0, S, ws.cvec + 4 * 256, CL);
+    a = dec_args(4, kv[0], ws.x);
     a.fin_w = Dk.norm_w; a.fin_b = Dk.norm_b; a.proj_w = (const uint4*)H->fin_w; a.proj_b = w->fin_b; a.feats = feats; a.F = F;
     return launch_layer_h(a, st);
 }

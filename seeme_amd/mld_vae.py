@@ -135,8 +135,14 @@ class MldVae(nn.Module):
         self.skel_embedding = nn.Linear(nfeats, d)
         self.final_layer = nn.Linear(d, nfeats)
 
-        self._wcache = None      # (fingerprint, VaeWeights struct, keep-alive tensors)
+        self._wcache = None      # (fingerprint, VaeWeights struct, keep-alive tensors, VaeWeightsH struct or None)
         self._ws = None          # workspace tensor (grow only)
+        self._dec_pro = {}       # {T: buffer} of the fp16 decoder's sample-independent prologue; dropped with _wcache
+
+    # The fp16 decoder's first-layer inputs depend on the weights and on T only: built once per (weight image, T) and read by every
+    # later decode.  False: decode never builds or passes a buffer (callers that decode at many distinct T).
+    dec_prologue_cache = True
+    _DEC_PRO_MAX = 8             # entries (about 0.5 MB each at T = 196); cleared when full
 
     # ------------------------------------------------------------------ weight image
     def _weights(self) -> L.VaeWeights:
@@ -190,6 +196,7 @@ class MldVae(nn.Module):
         keep += [fold_w, fold_b]
         w.ca_fold_w, w.ca_fold_b = fold_w.data_ptr(), fold_b.data_ptr()
         w.h16 = 0
+        h = None
         if self.precision == "fp16":
             h = L.VaeWeightsH()
             pk = lambda W: (keep.append(L.pack_mfma16(W, torch.float16)), keep[-1].data_ptr())[1]
@@ -203,8 +210,32 @@ class MldVae(nn.Module):
             h.emb_w, h.fin_w, h.ca_fold_w = pk(self.skel_embedding.weight), pk(self.final_layer.weight), pk(fold_w)
             keep.append(h)
             w.h16 = C.addressof(h)
-        self._wcache = (fpnt, w, keep)
+        self._wcache = (fpnt, w, keep, h)
+        self._dec_pro = {}
         return w
+
+    def _dec_prologue(self, w: L.VaeWeights, T: int, device) -> None:
+        """Point the fp16 weight image at the cached decoder prologue for T, building it on first use (never inside a graph
+        capture, where decode runs its own prologue launch instead)."""
+        h = self._wcache[3]
+        if h is None:
+            return
+        h.dec_pro, h.dec_pro_T = 0, 0
+        if not self.dec_prologue_cache:
+            return
+        buf = self._dec_pro.get(T)
+        if buf is None:
+            if torch.cuda.is_current_stream_capturing():
+                return
+            if len(self._dec_pro) >= self._DEC_PRO_MAX:
+                self._dec_pro.clear()
+            need = L.lib().seeme_vae_dec_prologue_bytes(T)
+            buf = torch.zeros(need, dtype=torch.uint8, device=device)
+            rc = L.lib().seeme_vae_dec_prologue_h16(C.byref(w), T, buf.data_ptr(), buf.numel(), L.current_stream())
+            L.check(rc, "seeme_vae_dec_prologue_h16")
+            torch.cuda.current_stream().synchronize()      # other streams may read the entry from here on
+            self._dec_pro[T] = buf
+        h.dec_pro, h.dec_pro_T = buf.data_ptr(), T
 
     def _workspace(self, B: int, T: int, device) -> torch.Tensor:
         need = L.lib().seeme_vae_workspace_bytes(B, T)
@@ -276,6 +307,7 @@ class MldVae(nn.Module):
         lens = self._lengths_tensor(lengths, z.device)
         ws = self._workspace(B, T, z.device)
         w = self._weights()
+        self._dec_prologue(w, T, z.device)
         rc = L.lib().seeme_vae_decode(C.byref(w), z2.data_ptr(), lens.data_ptr(), B, T, feats.data_ptr(),
                                       ws.data_ptr(), ws.numel(), L.current_stream())
         L.check(rc, "seeme_vae_decode")
