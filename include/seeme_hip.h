@@ -665,6 +665,30 @@ size_t seeme_scene_views_workspace_bytes(int N, int W, int P);           /* 0 fo
 int seeme_scene_views(const float* verts, const float* M, int N, int W, int P, float* cloud, int32_t* index, int32_t* count,
                       void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ interactee patches from raw frames (csrc/crop_patches.hip)
+ * The S x S patch that the reference's dataset cuts around the interactee with OpenCV (dataset.py:1664-1690: warpAffine,
+ * INTER_LINEAR, constant zero border, no flip, no rotation, no rescaling), for n patches in one launch.  frames [n_frames,H,W,3]
+ * uint8 RGB; frame_of_patch [n] int32 (several patches may name one frame, in any order); boxes [n,3] fp32 = cx, cy, b: the centre
+ * the reference hands to its warp and the side of the box in frame pixels (seeme_amd/crops.py patch_box); out [n,S,S,3] uint8.
+ * An integer definition, so the kernel and its plain-torch twin (crops.py crop_patches_torch) agree bit for bit.  In double, every
+ * product and sum rounded on its own: m = b / S, ox = cx - (S/2) m, oy = cy - (S/2) m; rne = round half to even; 64-bit integers,
+ * >> the arithmetic (flooring) shift:
+ *   X = (rne(ox 1024) + 16 + rne(m u 1024)) >> 5          (the two axes are NOT symmetric)
+ *   Y = (rne((m v + oy) 1024) + 16) >> 5
+ *   sx = X >> 5, ax = X & 31, sy = Y >> 5, ay = Y & 31
+ *   out[v,u,c] = ((32-ay)(32-ax) I[sy,sx,c] + (32-ay) ax I[sy,sx+1,c] + ay (32-ax) I[sy+1,sx,c] + ay ax I[sy+1,sx+1,c] + 512) >> 10
+ * A tap outside 0 <= row < H, 0 <= col < W contributes 0 and is never read.  1 <= H, W <= SEEME_CROP_FRAME_MAX, 1 <= S <=
+ * SEEME_CROP_PATCH_MAX, n >= 1 (not capped by the grid), n_frames >= 1; a frame's byte offset is computed in size_t.  The caller
+ * checks |cx|, |cy| <= SEEME_CROP_COORD_MAX, 0 < b <= SEEME_CROP_COORD_MAX, all finite, and 0 <= frame_of_patch < n_frames (the
+ * entry point cannot look into device memory without a synchronisation); inside these nothing overflows 64 bits.  The kernel
+ * guards itself as well: a patch whose box or frame index is outside them is all zeros, never an out-of-range read.  No
+ * allocation, no synchronisation, no atomics, no workspace; frame_of_patch and boxes 4-byte aligned, out any alignment. */
+#define SEEME_CROP_FRAME_MAX 16384
+#define SEEME_CROP_PATCH_MAX 1024
+#define SEEME_CROP_COORD_MAX 1048576            /* 2^20 */
+int seeme_crop_patches(const uint8_t* frames, int n_frames, int H, int W, const int32_t* frame_of_patch, const float* boxes,
+                       int n, int S, uint8_t* out, void* stream);
+
 /* ------------------------------------------------------------------ per-frame mesh metrics (csrc/mesh_metrics.hip)
  * Frame-level primitives of the EgoHMR tables (test_egohmr.py:463-492, 540-549): one float per frame, fp32 metres in and out, a
  * frame whose map entry is negative is skipped and gets 0; the caller averages over the valid frames of a sequence and chunks the

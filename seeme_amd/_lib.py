@@ -232,6 +232,7 @@ _SIGNATURES = {
     "seeme_stitch_windows": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp]),
     "seeme_scene_views_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "seeme_scene_views": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, C.c_size_t, fp]),
+    "seeme_crop_patches": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, fp, fp, C.c_int, C.c_int, fp, fp]),
     "seeme_pa_mpjpe_frames": (C.c_int, [fp, fp, fp, C.c_int, fp, fp]),
     "seeme_mesh_v2v_frames": (C.c_int, [fp, fp, fp, fp, fp, C.c_int, C.c_int, fp, fp]),
     "seeme_scene_min_dist2_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),

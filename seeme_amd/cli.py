@@ -459,7 +459,8 @@ def motion_to_smpl(motion: torch.Tensor, data_type: str, transl_in_feats: bool, 
 
 def predict_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=None) -> Dict:
     """predict.py: a recording .npz (``recording.load_recording``: the interactee's motion, optionally a scene cloud, image features
-    and the wearer's betas -- no wearer labels) -> the stitched SMPL motion of the wearer as an .npz."""
+    -- or, for an image_backbone model, video frames with the interactee's box, whose patches are cut on the device -- and the
+    wearer's betas -- no wearer labels) -> the stitched SMPL motion of the wearer as an .npz."""
     import numpy as np
     from . import recording as R
     p = build_parser("predict")
@@ -469,6 +470,8 @@ def predict_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=N
     g.add_argument("--overlap", type=int, default=None, help="override TEST.WINDOW_OVERLAP (frames shared by neighbouring windows)")
     g.add_argument("--seed", type=int, default=None, help="seed of the draws (default: SEED_VALUE)")
     g.add_argument("--save_hypotheses", action="store_true", help="also store m_rst_all [W,K,T,F], every window's K hypotheses")
+    g.add_argument("--video", type=str, default=None, help="decoded frames, uint8 RGB [Lf,H,W,3] as a .npy (opened memory-mapped), in "
+                   "place of the recording's video key; the recording holds center, scale and, for Lf < L, video_index")
     p.set_defaults(frames=None)                                         # the window length: MOTION_LENGTH unless --frames says otherwise
     p.set_defaults(scene_points=None)                                   # rows of a scene view: TEST.SCENE_VIEW_POINTS unless given
     args = p.parse_args(argv)
@@ -493,7 +496,7 @@ def predict_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=N
     if cfg.TEST.get("USE_EMA", False):
         log.info("EMA weights over %d tensors", overlay_ema(model, ck, ckpt))
     model = model.to(dev).eval()
-    rec = R.load_recording(args.input)
+    rec = R.load_recording(args.input, video=args.video)
     O = model.window_overlap if model.window_overlap is not None else T // 4
     moving = "world2cam" in rec                                         # every window in the camera frame of its first frame
     pelvis = R.rest_pelvis(model.smpl_model, torch.from_numpy(rec["betas"]).to(dev)[None])[0] if moving else None

@@ -37,7 +37,8 @@ On-disk layout (what the reference reads; the datasets themselves are licence-ga
     With ``image_backbone`` (model.image_backbone: the ResNet-50 runs in this package) the frames come as crops instead:
         <root>/image_crops_<split>.npy uint8 [F,224,224,3] RGB (the patch of dataset.py:1664-1690 before normalisation; opened
         memory-mapped, only the split's frames are read) and <root>/image_crop_names_<split>.npy, a unicode array [F] of the names.
-        The image slot of a batch is then uint8 NHWC [B,224,224,3]; the frame draw is the same.
+        The image slot of a batch is then uint8 NHWC [B,224,224,3]; the frame draw is the same.  ``crops.write_crop_files`` writes
+        both files from the frames.
 
 Files are read with loaders that execute nothing: ``np.load(allow_pickle=False)`` for arrays, and for the pickled ``.npy`` /
 ``.pkl`` containers an unpickler that only admits numpy array reconstruction and plain containers.

@@ -18,7 +18,9 @@ The model sees clips of T frames; a recording is cut into W overlapping windows 
 ``reframe_smpl`` / ``reframe_rot6d`` / ``reframe_joints``: a rigid map p -> A p + a applied to SMPL parameters and to joints, plain torch.
 
 ``load_recording`` / ``windows_batch`` read a recording ``.npz`` and cut it into a batch with the data module's tuple
-layout whose wearer slot is zero.  The definitions are stated once, in include/seeme_hip.h.
+layout whose wearer slot is zero; a recording may carry its image condition as raw video frames, whose patches around the interactee
+are then cut by ``crops.crop_patches_hip`` (``choose_frames``: which stored frame serves a window).  The definitions are stated once,
+in include/seeme_hip.h.
 """
 from __future__ import annotations
 
@@ -408,14 +410,80 @@ def _launch_scene_views(verts, M, P, ws=None, ws_bytes=None, out=None) -> Dict[s
 
 # ----------------------------------------------------------------------------- recording files
 _REC_KEYS = ("global_orient", "body_pose", "transl", "betas")
+_FRAME_KEYS = ("video", "video_index", "center", "scale", "image_crops")      # read in the file's own dtype
+_IMAGE_SOURCES = ("image_feats", "video", "image_crops")
 
 
-def load_recording(path: str) -> Dict[str, np.ndarray]:
+def _check_frames(rec, n: int, path: str) -> None:
+    """The frame keys of a recording with L = n frames: ONE image source, uint8 frames, a box per recording frame with video, and a
+    strictly increasing video_index inside 0..L-1 (made the identity when the file has none)."""
+    have = [k for k in _IMAGE_SOURCES if k in rec]
+    if len(have) > 1:
+        raise ValueError(f"{path}: holds {have}; a recording has ONE image source: image_feats, video or image_crops")
+    src = have[0] if have and have[0] != "image_feats" else None
+    if "video_index" in rec and src is None:
+        raise ValueError(f"{path}: video_index names the frames of video or image_crops, and the recording holds neither")
+    if src is None:
+        for k in ("center", "scale"):                                          # nothing reads them: float32 like every optional key
+            if k in rec:
+                rec[k] = np.asarray(rec[k], np.float32)
+        return
+    fr = rec[src]
+    tail = "[Lf,H,W,3]" if src == "video" else "[Lf,224,224,3]"
+    if fr.dtype != np.uint8 or fr.ndim != 4 or fr.shape[3] != 3 or fr.shape[0] < 1 or (src == "image_crops" and fr.shape[1:3] != (224, 224)):
+        raise ValueError(f"{path}: {src} is {fr.shape} {fr.dtype}: expected uint8 {tail} (RGB)")
+    if src == "video":
+        if min(fr.shape[1:3]) < 1 or max(fr.shape[1:3]) > 16384:
+            raise ValueError(f"{path}: video frames are {fr.shape[1]} x {fr.shape[2]}: H and W must be in 1..16384")
+        for k, shape in (("center", (n, 2)), ("scale", (n,))):
+            if k not in rec:
+                raise ValueError(f"{path}: video needs center [L,2] and scale [L], the interactee's box per frame; {k} is missing")
+            if rec[k].dtype.kind != "f" or rec[k].shape != shape:
+                raise ValueError(f"{path}: {k} is {rec[k].shape} {rec[k].dtype}: expected floats {list(shape)} (L = {n})")
+            rec[k] = np.asarray(rec[k], np.float32)
+    Lf = fr.shape[0]
+    if "video_index" not in rec:
+        if Lf != n:
+            raise ValueError(f"{path}: {src} holds {Lf} frames and the recording {n}: video_index [Lf] must say which they are")
+        rec["video_index"] = np.arange(n, dtype=np.int64)
+        return
+    vi = rec["video_index"]
+    if vi.dtype.kind not in "iu" or vi.shape != (Lf,):
+        raise ValueError(f"{path}: video_index is {vi.shape} {vi.dtype}: expected integers [{Lf}], one per frame of {src}")
+    vi = rec["video_index"] = vi.astype(np.int64)
+    if vi[0] < 0 or vi[-1] >= n or (np.diff(vi) <= 0).any():
+        raise ValueError(f"{path}: video_index must be strictly increasing inside 0..{n - 1} (L = {n}), got {vi[:8].tolist()}"
+                         f"{' ...' if Lf > 8 else ''} .. {int(vi[-1])}")
+
+
+def choose_frames(video_index, starts, lengths) -> List[int]:
+    """For every window [lo, lo + ln) the POSITION (row of video / image_crops) of the stored frame nearest to its centre frame
+    lo + ln // 2 among the stored frames inside the window; a tie goes to the earlier frame.  A window without a stored frame is
+    a ValueError that names it."""
+    vi = np.asarray(video_index, np.int64)
+    rows = []
+    for w, (lo, ln) in enumerate(zip(starts, lengths)):
+        a, b = int(np.searchsorted(vi, lo, "left")), int(np.searchsorted(vi, lo + ln, "left"))      # rows a..b-1 lie in the window
+        if a == b:
+            raise ValueError(f"windows_batch: window {w} (frames {lo}..{lo + ln - 1}) holds no stored video frame: video_index has "
+                             "none inside it")
+        d = np.abs(vi[a:b] - (lo + ln // 2))
+        rows.append(a + int(np.argmin(d)))                                     # (argmin: the first, so the earlier, of a tie)
+    return rows
+
+
+def load_recording(path: str, video: Optional[str] = None) -> Dict[str, np.ndarray]:
     """A recording ``.npz`` (read with allow_pickle=False: an object array is refused): the INTERACTEE's global_orient [L,3],
     body_pose [L,69|63], transl [L,3], betas [10]; optionally scene [P,3], image_feats [L,2048], wearer_betas [10].  float32.
     A moving camera adds world2cam [L,4,4], the rigid map from the recording's world frame to every frame's camera frame (float64:
     it is composed and inverted), and, in place of scene, scene_vertices [N,3]: the scene's vertices in the world frame, from which
-    every window's view is selected (``scene_views_hip``)."""
+    every window's view is selected (``scene_views_hip``).
+
+    The image condition has ONE source: image_feats, or video [Lf,H,W,3] uint8 RGB (decoded frames; needs center [L,2] and scale
+    [L], the interactee's box per recording frame, ``crops.patch_box``), or image_crops [Lf,224,224,3] uint8 (patches already cut).
+    video_index [Lf] integers names the recording frame of every stored frame, strictly increasing in 0..L-1; without it Lf = L and
+    it is the identity.  video and image_crops stay uint8.  `video`: a ``.npy`` of the frames, opened memory-mapped, in place of the
+    video key."""
     with np.load(path, allow_pickle=False) as z:
         missing = [k for k in _REC_KEYS if k not in z.files]
         if missing:
@@ -424,7 +492,13 @@ def load_recording(path: str) -> Dict[str, np.ndarray]:
                if k in z.files}
         if "world2cam" in z.files:
             rec["world2cam"] = np.asarray(z["world2cam"], np.float64)
+        rec.update({k: z[k] for k in _FRAME_KEYS if k in z.files})
+    if video is not None:
+        if "video" in rec:
+            raise ValueError(f"{path}: holds a video key and {video} was given as well; a recording has ONE image source")
+        rec["video"] = np.load(video, mmap_mode="r", allow_pickle=False)
     n = rec["global_orient"].shape[0]
+    _check_frames(rec, n, path)
     want = {"global_orient": [(n, 3)], "body_pose": [(n, 69), (n, 63)], "transl": [(n, 3)], "betas": [(10,)], "wearer_betas": [(10,)],
             "image_feats": [(n, 2048)]}
     if n < 1:
@@ -483,6 +557,11 @@ def windows_batch(rec, datamodule_or_stats, T: int, overlap: int, condition, dat
     normalised by the rule the data module applies at load time (``data.normalise_person`` / ``data.normalise_rot6d``: zero padding to
     T first); the wearer's slot (0) is all zeros.  A window's image features are those of its centre frame.  Returns (batch, starts,
     lengths).  datamodule_or_stats: a data module (``mean`` / ``std``) or the pair (mean, std).
+
+    A recording with video or image_crops instead of image_feats: the image slot is uint8 [W,224,224,3], for a model with
+    ``model.image_backbone``.  A window takes the stored frame nearest to its centre frame inside the window (``choose_frames``);
+    with video only those frames go to `device` and ONE ``crops.crop_patches_hip`` launch cuts their patches around
+    ``crops.patch_box`` of the frame's center / scale (without a ROCm `device`: ``crops.crop_patches_torch``, the same bytes).
 
     A moving camera: world2cam [L,4,4] (default: the recording's own key; without either nothing changes).  Window w is then put
     into the camera frame of its first frame, M_w = world2cam[starts[w]], as the data module does for training: the interactee's
@@ -547,10 +626,22 @@ def windows_batch(rec, datamodule_or_stats, T: int, overlap: int, condition, dat
         else:
             out.append(torch.from_numpy(rec["scene"])[None].expand(W, -1, -1).contiguous())
     if "image" in condition:
-        if "image_feats" not in rec:
+        if "video" in rec or "image_crops" in rec:                            # uint8 crops [W,224,224,3] for the model's backbone
+            from . import crops as CR
+            vi = rec["video_index"] if "video_index" in rec else np.arange(n)
+            rows = choose_frames(vi, starts, lengths)
+            if "video" in rec:                                                 # only the chosen frames go to the device: ONE launch
+                uniq, fop = np.unique(np.asarray(rows), return_inverse=True)
+                at = np.asarray(vi)[rows]                                      # their recording frames: the boxes' rows
+                frames = torch.from_numpy(np.ascontiguousarray(rec["video"][uniq]))
+                out.append(CR.crop_patches(frames, fop.reshape(-1), CR.boxes_of(rec["center"][at], rec["scale"][at]), CR.PATCH, device))
+            else:
+                out.append(torch.from_numpy(np.ascontiguousarray(rec["image_crops"][rows])))
+        elif "image_feats" not in rec:
             raise ValueError("windows_batch: the model has an 'image' condition and the recording holds no image_feats")
-        centre = [lo + ln // 2 for lo, ln in zip(starts, lengths)]
-        out.append(torch.from_numpy(rec["image_feats"][centre]).contiguous())
+        else:
+            centre = [lo + ln // 2 for lo, ln in zip(starts, lengths)]
+            out.append(torch.from_numpy(rec["image_feats"][centre]).contiguous())
     out.append(length)
     if device is not None:
         out = [t.to(device) for t in out]
