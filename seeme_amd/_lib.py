@@ -280,6 +280,59 @@ def check(rc: int, what: str = ""):
         raise SeemeError(f"{what or 'seeme_hip'} failed (rc={rc}): {msg}")
 
 
+def call(name: str, *args):
+    """Invoke the status-returning entry point `name` with `args` as they are; a non-zero status raises SeemeError labelled `name`."""
+    check(getattr(lib(), name)(*args), name)
+
+
+class Workspace:
+    """Grow-only scratch bytes for the launches that take a workspace.
+
+    One uint8 buffer is held per key.  A request that fits gets the held tensor itself (all of it, not a slice); one that does not
+    drops the held buffer first and then allocates, so the peak is the larger of the two and not their sum.
+
+    The key is the device (`per_stream=False`), or the device plus the current stream's handle (`per_stream=True`; on a CPU device
+    there is no stream and the key is the device alone).  A CUDA device without an index counts as the current one.  Buffers of
+    other keys stay held: an object used on two devices keeps one buffer on each.  Both kinds exist for a reason:
+
+    per_stream=False  the model objects (MldVae, MldDenoiser, ResnetPointnet, ResNet50, SMPL).  Their launches are warmed up on one
+                      stream and captured on another (bench.py --graph; MLD.capture_training_step warms up on a side stream and
+                      captures under torch.cuda.graph's own), so a buffer keyed by stream would be allocated for the first time
+                      inside the capture.  One object's launches must therefore not overlap on two streams.
+    per_stream=True   the module-level caches of the metric and recording functions, which any stream may call: launches of one
+                      stream run in order, so they can share scratch, and launches of two streams never meet in one buffer.
+    """
+
+    def __init__(self, per_stream: bool):
+        self.per_stream = per_stream
+        self._held = {}
+
+    def get(self, need: int, device):
+        """uint8 tensor on `device` with numel() >= max(need, 16): the whole held buffer."""
+        import torch
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        key = device
+        if self.per_stream and device.type == "cuda":
+            key = (device, torch.cuda.current_stream(device).cuda_stream)
+        ws = self._held.get(key)
+        if ws is None or ws.numel() < max(need, 16):
+            ws = None
+            self._held.pop(key, None)
+            ws = self._held[key] = torch.empty(max(int(need), 16), dtype=torch.uint8, device=device)
+        return ws
+
+    def cached(self) -> list:
+        """Every buffer currently held."""
+        return list(self._held.values())
+
+    def fill_(self, byte: int):
+        """Overwrite every held buffer: no launch may depend on what an earlier one left (tests/test_gpu_vae_edges.py poisons it)."""
+        for ws in self._held.values():
+            ws.fill_(byte)
+
+
 def default_xcds(chains: int, want="auto") -> int:
     """How many XCDs the working workgroups of a one-CU-per-chain launch sit on (SeemeSampleArgs.xcds): `want` = "auto" packs ~16
     chains per XCD -- right for a launch that has the chip to itself (one stream); callers that keep several launches in flight

@@ -132,9 +132,8 @@ def crop_patches_hip(frames, frame_of_patch, boxes, S: int = PATCH) -> torch.Ten
 def _launch(frames, fop_dev, boxes_dev, S: int, out) -> None:
     """The C entry as it is (no host checks: the tests hand it boxes outside the preconditions)."""
     with torch.cuda.device(frames.device):
-        L.check(L.lib().seeme_crop_patches(frames.data_ptr(), int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2]),
-                                           fop_dev.data_ptr(), boxes_dev.data_ptr(), int(fop_dev.shape[0]), int(S), out.data_ptr(),
-                                           L.current_stream()), "seeme_crop_patches")
+        L.call("seeme_crop_patches", frames.data_ptr(), int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2]),
+               fop_dev.data_ptr(), boxes_dev.data_ptr(), int(fop_dev.shape[0]), int(S), out.data_ptr(), L.current_stream())
 
 
 def crop_patches(frames, frame_of_patch, boxes, S: int = PATCH, device=None) -> torch.Tensor:

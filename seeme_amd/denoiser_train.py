@@ -34,7 +34,7 @@ _MATS = ("skip", "inp", "outp", "l1", "l2", "caq", "cao", "f1", "f2", "fo")
 def _train_layout():
     n = 54
     buf = (C.c_int64 * n)()
-    L.check(L.lib().seeme_den_train_layout(buf, n), "seeme_den_train_layout")
+    L.call("seeme_den_train_layout", buf, n)
     v = list(buf)
     return {"bwd_total": v[50], "DT_TOTAL": v[51], "DB_TOTAL": v[52], "DB_LAYER": v[53]}
 
@@ -204,11 +204,10 @@ class TrainPack:
         B = gout.shape[0]
         DBL = self.lay["DB_LAYER"]
         if self.bound and gout.is_cuda:
-            L.check(L.lib().seeme_den_wgrad(gout.data_ptr(), gout.shape[1], B, self._wgrad_tiles.data_ptr(), self._n_wgrad_tiles,
-                                            self.gflat.data_ptr(), L.current_stream()), "seeme_den_wgrad")
-            L.check(L.lib().seeme_den_vecgrad(gout.data_ptr(), gout.shape[1], B, self.gather_idx.data_ptr(), self.gather_idx.numel(),
-                                              self.vec_region.data_ptr(), self.dx0_span[0], self.dpe.data_ptr(), L.current_stream()),
-                    "seeme_den_vecgrad")
+            L.call("seeme_den_wgrad", gout.data_ptr(), gout.shape[1], B, self._wgrad_tiles.data_ptr(), self._n_wgrad_tiles,
+                   self.gflat.data_ptr(), L.current_stream())
+            L.call("seeme_den_vecgrad", gout.data_ptr(), gout.shape[1], B, self.gather_idx.data_ptr(), self.gather_idx.numel(),
+                   self.vec_region.data_ptr(), self.dx0_span[0], self.dpe.data_ptr(), L.current_stream())
             if self._attached:                                 # GradBucket.prepare() made .grad these very views
                 self._attached = False
                 if self.bucket is not None:
@@ -226,8 +225,8 @@ class TrainPack:
         colsum = gout.sum(0)
         G = gout[:, : 5 * DBL].view(B, 5, DBL)
         if gout.is_cuda:
-            L.check(L.lib().seeme_den_wgrad(gout.data_ptr(), gout.shape[1], B, self._wgrad_tiles.data_ptr(), self._n_wgrad_tiles,
-                                            flat.data_ptr(), L.current_stream()), "seeme_den_wgrad")
+            L.call("seeme_den_wgrad", gout.data_ptr(), gout.shape[1], B, self._wgrad_tiles.data_ptr(), self._n_wgrad_tiles,
+                   flat.data_ptr(), L.current_stream())
         else:                                                                         # (CPU: shape tests of the host logic)
             for name, ls, off, Nn, K in self.mat_blocks:
                 xo, _, yo, _ = _LIN[name]
@@ -252,8 +251,8 @@ class TrainPack:
         return tuple(t.data_ptr() for t in self.params) != self._ptr_key
 
     def refresh(self):
-        L.check(L.lib().seeme_den_train_pack(self._ptrs, self.img_f.data_ptr(), self.img_b.data_ptr(), self._vsrc, self._vn,
-                                             self._vdst, self._nvec, self.vp.data_ptr(), L.current_stream()), "seeme_den_train_pack")
+        L.call("seeme_den_train_pack", self._ptrs, self.img_f.data_ptr(), self.img_b.data_ptr(), self._vsrc, self._vn, self._vdst,
+               self._nvec, self.vp.data_ptr(), L.current_stream())
 
 
 DROP_BYTES = 10960          # SEEME_DEN_DROP_BYTES: 5 layers x 2192 mask bytes per sample (csrc/den_train.h DM_*)
@@ -316,7 +315,7 @@ class _Chain(torch.autograd.Function):
         masks, scale = draw_dropout_masks(pack.den, B)
         a.drop, a.drop_scale = L.ptr(masks), scale
         a.xcds = L.default_xcds(B)
-        L.check(L.lib().seeme_denoiser_sample(C.byref(pack.w), C.byref(a), L.current_stream()), "seeme_denoiser_sample")
+        L.call("seeme_denoiser_sample", C.byref(pack.w), C.byref(a), L.current_stream())
         ctx.pack, ctx.N, ctx.masks, ctx.drop_scale = pack, N, masks, scale
         pack.last_masks = masks
         ctx.save_for_backward(save, ctab, ttab, trow)
@@ -330,10 +329,9 @@ class _Chain(torch.autograd.Function):
         lay = pack.lay
         gout = torch.zeros(B, lay["DB_TOTAL"], device=dev, dtype=torch.float32)
         dctab, dttab = torch.empty_like(ctab), torch.empty_like(ttab)
-        L.check(L.lib().seeme_denoiser_backward_drop(C.byref(pack.w), pack.img_b.data_ptr(), B, N, save.data_ptr(), ctab.data_ptr(),
-                                                      ttab.data_ptr(), trow.data_ptr(), dout.contiguous().data_ptr(), gout.data_ptr(),
-                                                      dctab.data_ptr(), dttab.data_ptr(), L.ptr(ctx.masks), ctx.drop_scale,
-                                                      L.default_xcds(B), L.current_stream()), "seeme_denoiser_backward")
+        L.call("seeme_denoiser_backward_drop", C.byref(pack.w), pack.img_b.data_ptr(), B, N, save.data_ptr(), ctab.data_ptr(),
+               ttab.data_ptr(), trow.data_ptr(), dout.contiguous().data_ptr(), gout.data_ptr(), dctab.data_ptr(), dttab.data_ptr(),
+               L.ptr(ctx.masks), ctx.drop_scale, L.default_xcds(B), L.current_stream())
         # the chain's own parameters do not travel through autograd: their gradients are reduced straight into .grad
         pack.reduce_into_grads(gout)
         fin = 5 * lay["DB_LAYER"]

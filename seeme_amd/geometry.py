@@ -12,7 +12,7 @@ def _run(op: int, x: torch.Tensor, in_w: int, out_shape):
     x2 = x.reshape(-1, in_w).contiguous()
     M = x2.shape[0]
     out = torch.empty((M,) + out_shape, device=x.device, dtype=torch.float32)
-    L.check(L.lib().seeme_geometry(op, x2.data_ptr(), out.data_ptr(), M, L.current_stream()), "seeme_geometry")
+    L.call("seeme_geometry", op, x2.data_ptr(), out.data_ptr(), M, L.current_stream())
     return out
 
 
@@ -37,8 +37,7 @@ def rot6d_to_rotmat(x: torch.Tensor, rot6d_mode: str = "prohmr") -> torch.Tensor
 
 def _renorm_launch(f2: torch.Tensor, m: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
     out = torch.empty_like(f2)
-    L.check(L.lib().seeme_renorm(f2.data_ptr(), m.data_ptr(), s.data_ptr(), out.data_ptr(), f2.shape[0], f2.shape[1],
-                                  L.current_stream()), "seeme_renorm")
+    L.call("seeme_renorm", f2.data_ptr(), m.data_ptr(), s.data_ptr(), out.data_ptr(), f2.shape[0], f2.shape[1], L.current_stream())
     return out
 
 

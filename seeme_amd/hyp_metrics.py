@@ -65,7 +65,7 @@ def hyp_metrics_torch(jts_pred_all, jts_ref, lengths) -> Dict[str, torch.Tensor]
     return out
 
 
-_WS: Dict[tuple, torch.Tensor] = {}
+_WS = L.Workspace(per_stream=True)    # shared by _launch and _launch_pairdist: launches of one stream run in order
 
 
 def hyp_metrics_hip(jts_pred_all, jts_ref, lengths) -> Dict[str, torch.Tensor]:
@@ -88,15 +88,11 @@ def _launch(pred, ref, lens, B, K, T, ws_bytes=None) -> Dict[str, torch.Tensor]:
     dev = ref.device
     lib = L.lib()
     need = int(lib.seeme_hyp_metrics_workspace_bytes(B, K, T))
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < max(need, 16):
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        _WS[key] = ws
+    ws = _WS.get(need, dev)
     per_hyp = torch.empty(3, B, max(K, 0), device=dev, dtype=torch.float32)
     per_seq = torch.empty(2, B, device=dev, dtype=torch.float32)
-    L.check(lib.seeme_hyp_metrics(pred.data_ptr(), ref.data_ptr(), lens.data_ptr(), B, K, T, per_hyp.data_ptr(), per_seq.data_ptr(),
-                                  ws.data_ptr(), need if ws_bytes is None else ws_bytes, L.current_stream()), "seeme_hyp_metrics")
+    L.call("seeme_hyp_metrics", pred.data_ptr(), ref.data_ptr(), lens.data_ptr(), B, K, T, per_hyp.data_ptr(), per_seq.data_ptr(),
+           ws.data_ptr(), need if ws_bytes is None else ws_bytes, L.current_stream())
     out = {n: per_hyp[i] for i, n in enumerate(PER_HYP)}
     out.update({n: per_seq[i] for i, n in enumerate(PER_SEQ)})
     return out
@@ -145,15 +141,11 @@ def _launch_pairdist(pred, lens, B, K, T, ws_bytes=None) -> Dict[str, torch.Tens
     dev = lens.device
     lib = L.lib()
     need = int(lib.seeme_hyp_pairdist_workspace_bytes(B, K, T))
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _WS.get(key)                        # the per-stream workspace of _launch: launches of one stream run in order
-    if ws is None or ws.numel() < max(need, 16):
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        _WS[key] = ws
+    ws = _WS.get(need, dev)
     dist = torch.empty(B, max(K, 0), max(K, 0), device=dev, dtype=torch.float32)
     medoid = torch.empty(B, device=dev, dtype=torch.int32)
-    L.check(lib.seeme_hyp_pairdist(pred.data_ptr(), lens.data_ptr(), B, K, T, dist.data_ptr(), medoid.data_ptr(), ws.data_ptr(),
-                                   need if ws_bytes is None else ws_bytes, L.current_stream()), "seeme_hyp_pairdist")
+    L.call("seeme_hyp_pairdist", pred.data_ptr(), lens.data_ptr(), B, K, T, dist.data_ptr(), medoid.data_ptr(), ws.data_ptr(),
+           need if ws_bytes is None else ws_bytes, L.current_stream())
     return {"PAIR_DIST": dist, "medoid_index": medoid.long()}
 
 

@@ -257,8 +257,7 @@ def pa_mpjpe_hip(j_pred, j_ref, ref_of_frame=None) -> torch.Tensor:
     _check_map(m, int(j_ref.shape[0]), "pa_mpjpe")
     jp, jr = j_pred.contiguous(), j_ref.contiguous()
     out = torch.empty(max(F, 0), device=j_pred.device, dtype=torch.float32)
-    L.check(L.lib().seeme_pa_mpjpe_frames(jp.data_ptr(), jr.data_ptr(), m.data_ptr(), F, out.data_ptr(), L.current_stream()),
-            "seeme_pa_mpjpe_frames")
+    L.call("seeme_pa_mpjpe_frames", jp.data_ptr(), jr.data_ptr(), m.data_ptr(), F, out.data_ptr(), L.current_stream())
     return out
 
 
@@ -277,12 +276,12 @@ def v2v_hip(v_pred, pel_pred, v_ref, pel_ref, ref_of_frame=None) -> torch.Tensor
     al = lambda t: t.contiguous() if t.contiguous().data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
     vp, pp, vr, pr = al(v_pred), pel_pred.contiguous(), al(v_ref), pel_ref.contiguous()
     out = torch.empty(max(F, 0), device=v_pred.device, dtype=torch.float32)
-    L.check(L.lib().seeme_mesh_v2v_frames(vp.data_ptr(), pp.data_ptr(), vr.data_ptr(), pr.data_ptr(), m.data_ptr(), F, V,
-                                          out.data_ptr(), L.current_stream()), "seeme_mesh_v2v_frames")
+    L.call("seeme_mesh_v2v_frames", vp.data_ptr(), pp.data_ptr(), vr.data_ptr(), pr.data_ptr(), m.data_ptr(), F, V, out.data_ptr(),
+           L.current_stream())
     return out
 
 
-_WS: Dict[tuple, torch.Tensor] = {}
+_WS = L.Workspace(per_stream=True)    # shared by scene_min_dist2 and scene_inside_count: launches of one stream run in order
 
 
 def scene_min_dist2_hip(verts, scene, scene_of_frame=None, ws_bytes=None) -> torch.Tensor:
@@ -297,17 +296,11 @@ def scene_min_dist2_hip(verts, scene, scene_of_frame=None, ws_bytes=None) -> tor
     _check_map(m, S, "scene_min_dist2")
     lib = L.lib()
     need = int(lib.seeme_scene_min_dist2_workspace_bytes(F, V, S, P))
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < max(need, 16):
-        ws = None
-        _WS.pop(key, None)
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        _WS[key] = ws
+    ws = _WS.get(need, dev)
     vs, sc = verts.contiguous(), scene.contiguous()
     out = torch.empty(max(F, 0), device=dev, dtype=torch.float32)
-    L.check(lib.seeme_scene_min_dist2(vs.data_ptr(), sc.data_ptr(), m.data_ptr(), F, V, S, P, out.data_ptr(), ws.data_ptr(),
-                                      need if ws_bytes is None else ws_bytes, L.current_stream()), "seeme_scene_min_dist2")
+    L.call("seeme_scene_min_dist2", vs.data_ptr(), sc.data_ptr(), m.data_ptr(), F, V, S, P, out.data_ptr(), ws.data_ptr(),
+           need if ws_bytes is None else ws_bytes, L.current_stream())
     return out
 
 
@@ -349,12 +342,9 @@ def winding_number_hip(verts, faces, points, points_of_frame=None) -> torch.Tens
     _check_map(m, S, "winding_number")
     vs, pt = verts.contiguous(), points.contiguous()
     out = torch.empty(max(F, 0), max(P, 0), device=dev, dtype=torch.float32)
-    L.check(L.lib().seeme_mesh_winding(vs.data_ptr(), fa.data_ptr(), int(fa.shape[0]), pt.data_ptr(), m.data_ptr(), F, V, S, P,
-                                       out.data_ptr(), L.current_stream()), "seeme_mesh_winding")
+    L.call("seeme_mesh_winding", vs.data_ptr(), fa.data_ptr(), int(fa.shape[0]), pt.data_ptr(), m.data_ptr(), F, V, S, P,
+           out.data_ptr(), L.current_stream())
     return out
-
-
-_WS_COUNT: Dict[tuple, torch.Tensor] = {}
 
 
 def scene_inside_count_hip(verts, faces, scene, scene_of_frame=None, ws_bytes=None) -> torch.Tensor:
@@ -366,18 +356,11 @@ def scene_inside_count_hip(verts, faces, scene, scene_of_frame=None, ws_bytes=No
     _check_map(m, S, "scene_inside_count")
     lib = L.lib()
     need = int(lib.seeme_scene_inside_count_workspace_bytes(F, V, S, P))
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _WS_COUNT.get(key)
-    if ws is None or ws.numel() < max(need, 16):
-        ws = None
-        _WS_COUNT.pop(key, None)
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        _WS_COUNT[key] = ws
+    ws = _WS.get(need, dev)
     vs, sc = verts.contiguous(), scene.contiguous()
     out = torch.empty(max(F, 0), device=dev, dtype=torch.int32)
-    L.check(lib.seeme_scene_inside_count(vs.data_ptr(), fa.data_ptr(), int(fa.shape[0]), sc.data_ptr(), m.data_ptr(), F, V, S, P,
-                                         out.data_ptr(), ws.data_ptr(), need if ws_bytes is None else ws_bytes, L.current_stream()),
-            "seeme_scene_inside_count")
+    L.call("seeme_scene_inside_count", vs.data_ptr(), fa.data_ptr(), int(fa.shape[0]), sc.data_ptr(), m.data_ptr(), F, V, S, P,
+           out.data_ptr(), ws.data_ptr(), need if ws_bytes is None else ws_bytes, L.current_stream())
     return out
 
 

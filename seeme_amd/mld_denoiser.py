@@ -190,7 +190,7 @@ class MldDenoiser(nn.Module):
         self.encoder = _SkipStackParams(lambda: _MDLayerParams(d, ff_size, num_heads, dropout), num_layers, d)
 
         self._wcache = None
-        self._ws = None
+        self._ws = L.Workspace(per_stream=False)
         self._table_cache = {}
         self._ccache = {}
         self._xchg = None
@@ -199,7 +199,7 @@ class MldDenoiser(nn.Module):
     def _layout(self):
         n = 5 * len(_LAYER_FIELDS) + 5
         buf = (C.c_int64 * n)()
-        L.check(L.lib().seeme_den_layout(1024, self.ff_size, buf, n), "seeme_den_layout")
+        L.call("seeme_den_layout", 1024, self.ff_size, buf, n)
         vals = list(buf)
         layers = [dict(zip(_LAYER_FIELDS, vals[i * 30:(i + 1) * 30])) for i in range(5)]
         pe0, fnw, fnb, wg_total, vp_total = vals[150:155]
@@ -329,7 +329,7 @@ class MldDenoiser(nn.Module):
         code = {"fp32": 0, "bf16": 1, "fp16": 2}[self.weight_dtype]
         wdt = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[self.weight_dtype]
         lo = (C.c_int64 * 14)()
-        L.check(L.lib().seeme_den_cluster_layout(Cc, code, int(query), lo, 14), "seeme_den_cluster_layout")
+        L.call("seeme_den_cluster_layout", Cc, code, int(query), lo, 14)
         NU, UB, total, UL, KL = (int(v) for v in lo[:5])
         U_D, U_G, U_H = int(lo[9]), int(lo[12]), int(lo[13])
         EPL = KL // 4                                   # elements per lane per wave-load (16 B)
@@ -425,10 +425,7 @@ class MldDenoiser(nn.Module):
         return int(hdr[0]), int(hdr[1])
 
     def _workspace(self, rows: int, device):
-        need = L.lib().seeme_denoiser_workspace_bytes(rows, 0, 0)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
-        return self._ws
+        return self._ws.get(L.lib().seeme_denoiser_workspace_bytes(rows, 0, 0), device)
 
     # ------------------------------------------------------------------ tables
     def time_tables(self, tfeat: torch.Tensor) -> torch.Tensor:
@@ -439,9 +436,8 @@ class MldDenoiser(nn.Module):
         ttab = torch.empty(rows, L.TROW, device=tfeat.device, dtype=torch.float32)
         ws = self._workspace(rows, tfeat.device)
         w = self._weights()
-        L.check(L.lib().seeme_denoiser_time_tables(C.byref(w), tfeat.data_ptr(), rows, ttab.data_ptr(),
-                                                    ws.data_ptr(), ws.numel(), L.current_stream()),
-                "seeme_denoiser_time_tables")
+        L.call("seeme_denoiser_time_tables", C.byref(w), tfeat.data_ptr(), rows, ttab.data_ptr(), ws.data_ptr(), ws.numel(),
+               L.current_stream())
         return ttab
 
     def cond_tables(self, cond_bf: torch.Tensor) -> torch.Tensor:
@@ -451,8 +447,7 @@ class MldDenoiser(nn.Module):
         Bc, N, _ = cond_bf.shape
         ctab = torch.empty(Bc, N, L.CROW, device=cond_bf.device, dtype=torch.float32)
         w = self._weights()
-        L.check(L.lib().seeme_denoiser_cond_tables(C.byref(w), cond_bf.data_ptr(), Bc, N, ctab.data_ptr(), 0, 0,
-                                                    L.current_stream()), "seeme_denoiser_cond_tables")
+        L.call("seeme_denoiser_cond_tables", C.byref(w), cond_bf.data_ptr(), Bc, N, ctab.data_ptr(), 0, 0, L.current_stream())
         return ctab
 
     def ca_tables(self, ctab: torch.Tensor, ttab: torch.Tensor, trow: torch.Tensor, per_sample: bool) -> torch.Tensor:
@@ -463,9 +458,8 @@ class MldDenoiser(nn.Module):
         catab = torch.empty(Bc, R, 5, self.latent_dim, device=ctab.device, dtype=torch.float32)
         ws = torch.empty(5 * Bc * R * 256, device=ctab.device, dtype=torch.float32)
         w = self._weights()
-        L.check(L.lib().seeme_denoiser_ca_tables(C.byref(w), ctab.data_ptr(), ttab.data_ptr(), trow.data_ptr(), int(per_sample),
-                                                  trow.numel(), Bc, catab.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-                                                  L.current_stream()), "seeme_denoiser_ca_tables")
+        L.call("seeme_denoiser_ca_tables", C.byref(w), ctab.data_ptr(), ttab.data_ptr(), trow.data_ptr(), int(per_sample),
+               trow.numel(), Bc, catab.data_ptr(), ws.data_ptr(), ws.numel() * 4, L.current_stream())
         return catab
 
     def _launch(self, latents2d, ctab, ttab, trow, per_sample, steps, sched, coef, noise, cfg, guidance):
@@ -492,10 +486,9 @@ class MldDenoiser(nn.Module):
             cl.xchg, cl.xchg_bytes = self._xchg.data_ptr(), self._xchg.numel()
             cl.query = int(N > 1)
             cl.samples = spc
-            L.check(L.lib().seeme_denoiser_sample_cluster(C.byref(w), C.byref(cl), C.byref(a), L.current_stream()),
-                    "seeme_denoiser_sample_cluster")
+            L.call("seeme_denoiser_sample_cluster", C.byref(w), C.byref(cl), C.byref(a), L.current_stream())
             return out
-        L.check(L.lib().seeme_denoiser_sample(C.byref(w), C.byref(a), L.current_stream()), "seeme_denoiser_sample")
+        L.call("seeme_denoiser_sample", C.byref(w), C.byref(a), L.current_stream())
         return out
 
     # ------------------------------------------------------------------ reference API

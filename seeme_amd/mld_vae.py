@@ -136,7 +136,7 @@ class MldVae(nn.Module):
         self.final_layer = nn.Linear(d, nfeats)
 
         self._wcache = None      # (fingerprint, VaeWeights struct, keep-alive tensors, VaeWeightsH struct or None)
-        self._ws = None          # workspace tensor (grow only)
+        self._ws = L.Workspace(per_stream=False)
         self._dec_pro = {}       # {T: buffer} of the fp16 decoder's sample-independent prologue; dropped with _wcache
 
     # The fp16 decoder's first-layer inputs depend on the weights and on T only: built once per (weight image, T) and read by every
@@ -231,17 +231,13 @@ class MldVae(nn.Module):
                 self._dec_pro.clear()
             need = L.lib().seeme_vae_dec_prologue_bytes(T)
             buf = torch.zeros(need, dtype=torch.uint8, device=device)
-            rc = L.lib().seeme_vae_dec_prologue_h16(C.byref(w), T, buf.data_ptr(), buf.numel(), L.current_stream())
-            L.check(rc, "seeme_vae_dec_prologue_h16")
+            L.call("seeme_vae_dec_prologue_h16", C.byref(w), T, buf.data_ptr(), buf.numel(), L.current_stream())
             torch.cuda.current_stream().synchronize()      # other streams may read the entry from here on
             self._dec_pro[T] = buf
         h.dec_pro, h.dec_pro_T = buf.data_ptr(), T
 
     def _workspace(self, B: int, T: int, device) -> torch.Tensor:
-        need = L.lib().seeme_vae_workspace_bytes(B, T)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
-        return self._ws
+        return self._ws.get(L.lib().seeme_vae_workspace_bytes(B, T), device)
 
     @staticmethod
     def _lengths_tensor(lengths, device) -> torch.Tensor:
@@ -279,10 +275,8 @@ class MldVae(nn.Module):
         lens = self._lengths_tensor(lengths, features.device)
         ws = self._workspace(B, T, features.device)
         w = self._weights()
-        rc = L.lib().seeme_vae_encode(C.byref(w), features.data_ptr(), lens.data_ptr(), B, T,
-                                      dist.data_ptr(), dist[1].data_ptr(), ws.data_ptr(), ws.numel(),
-                                      L.current_stream())
-        L.check(rc, "seeme_vae_encode")
+        L.call("seeme_vae_encode", C.byref(w), features.data_ptr(), lens.data_ptr(), B, T, dist.data_ptr(), dist[1].data_ptr(),
+               ws.data_ptr(), ws.numel(), L.current_stream())
         return dist
 
     def encode(self, features: torch.Tensor, images: Optional[torch.Tensor] = None,
@@ -308,7 +302,6 @@ class MldVae(nn.Module):
         ws = self._workspace(B, T, z.device)
         w = self._weights()
         self._dec_prologue(w, T, z.device)
-        rc = L.lib().seeme_vae_decode(C.byref(w), z2.data_ptr(), lens.data_ptr(), B, T, feats.data_ptr(),
-                                      ws.data_ptr(), ws.numel(), L.current_stream())
-        L.check(rc, "seeme_vae_decode")
+        L.call("seeme_vae_decode", C.byref(w), z2.data_ptr(), lens.data_ptr(), B, T, feats.data_ptr(), ws.data_ptr(), ws.numel(),
+               L.current_stream())
         return feats

@@ -240,8 +240,8 @@ class FusedAdamWStep(_EmaClipOptions):
         a.ema_decay, a.ema_warmup = self.ema_decay, int(self.ema_warmup)
         if self.grad_clip_norm > 0.0:
             out, ws = self.last_grad_norm, self._gn_ws
-            L.check(L.lib().seeme_grad_norm(a.chunks, a.n_chunks, a.grads, self.grad_clip_norm, out.data_ptr(), ws.data_ptr(),
-                                            ws.numel() * 8, L.current_stream()), "seeme_grad_norm")
+            L.call("seeme_grad_norm", a.chunks, a.n_chunks, a.grads, self.grad_clip_norm, out.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                   L.current_stream())
             a.grad_scale = out.data_ptr() + 4
         if device_step:
             sc = self._device_scalars(group, shared, self._chunks.device)
@@ -254,7 +254,7 @@ class FusedAdamWStep(_EmaClipOptions):
             shared.fill_(step)
             self._refresh_device_step(group, shared)
             a.lr, a.step = float(group["lr"]), step
-        L.check(L.lib().seeme_adamw_step_ex(C.byref(a), L.current_stream()), "seeme_adamw_step_ex")
+        L.call("seeme_adamw_step_ex", C.byref(a), L.current_stream())
 
     @torch.no_grad()
     def step(self, device_step: bool = False):
@@ -305,18 +305,16 @@ class FusedAdamWStep(_EmaClipOptions):
                 sc[0:1].add_(1.0)
                 if not capturing:
                     shared.add_(1.0)
-                L.check(L.lib().seeme_adamw_step_dev(self._chunks.data_ptr(), self._n_chunks, self._p.data_ptr(), gp.data_ptr(),
-                                                     self._m.data_ptr(), self._v.data_ptr(), sc.data_ptr(), float(b1), float(b2),
-                                                     float(group["eps"]), float(group["weight_decay"]), L.current_stream()),
-                        "seeme_adamw_step_dev")
+                L.call("seeme_adamw_step_dev", self._chunks.data_ptr(), self._n_chunks, self._p.data_ptr(), gp.data_ptr(),
+                       self._m.data_ptr(), self._v.data_ptr(), sc.data_ptr(), float(b1), float(b2), float(group["eps"]),
+                       float(group["weight_decay"]), L.current_stream())
             else:
                 step = float(shared) + 1.0
                 shared.fill_(step)
                 self._refresh_device_step(group, shared)  # the device-side count (if any) follows the host's
-                L.check(L.lib().seeme_adamw_step(self._chunks.data_ptr(), self._n_chunks, self._p.data_ptr(), gp.data_ptr(),
-                                                 self._m.data_ptr(), self._v.data_ptr(), float(group["lr"]), float(b1), float(b2),
-                                                 float(group["eps"]), float(group["weight_decay"]), float(step),
-                                                 L.current_stream()), "seeme_adamw_step")
+                L.call("seeme_adamw_step", self._chunks.data_ptr(), self._n_chunks, self._p.data_ptr(), gp.data_ptr(),
+                       self._m.data_ptr(), self._v.data_ptr(), float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                       float(group["weight_decay"]), float(step), L.current_stream())
             self._keep = (grads, gp)                      # alive until the next step (the launch is asynchronous)
         self._updated = updated
         torch.autograd.graph.increment_version(updated)

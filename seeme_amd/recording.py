@@ -312,16 +312,7 @@ def reframe_joints(joints, J0, A, a, has_transl: bool):
 
 
 # ----------------------------------------------------------------------------- kernels
-_WS: Dict[tuple, torch.Tensor] = {}
-
-
-def _workspace(dev, need: int) -> torch.Tensor:
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)             # per stream: launches of one stream run in order
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < max(need, 16):
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        _WS[key] = ws
-    return ws
+_WS = L.Workspace(per_stream=True)    # shared by the launches below: launches of one stream run in order
 
 
 def overlap_cost_hip(jts, overlap: int) -> torch.Tensor:
@@ -336,11 +327,11 @@ def overlap_cost_hip(jts, overlap: int) -> torch.Tensor:
 def _launch_overlap(jts, W, K, T, O, ws_bytes=None) -> torch.Tensor:
     lib = L.lib()
     need = int(lib.seeme_overlap_cost_workspace_bytes(W, K, T, O))
-    ws = _workspace(jts.device, need)
+    ws = _WS.get(need, jts.device)
     # (the kernel writes nothing for O = 0: the cost of sharing no frame is 0)
     cost = (torch.zeros if O == 0 else torch.empty)(max(W - 1, 0), max(K, 0), max(K, 0), device=jts.device, dtype=torch.float32)
-    L.check(lib.seeme_overlap_cost(jts.data_ptr(), W, K, T, O, cost.data_ptr(), ws.data_ptr(), need if ws_bytes is None else ws_bytes,
-                                   L.current_stream()), "seeme_overlap_cost")
+    L.call("seeme_overlap_cost", jts.data_ptr(), W, K, T, O, cost.data_ptr(), ws.data_ptr(), need if ws_bytes is None else ws_bytes,
+           L.current_stream())
     return cost
 
 
@@ -360,12 +351,12 @@ def _launch_path(cost, unary, W, K, ws_bytes=None) -> Dict[str, torch.Tensor]:
     dev = cost.device
     lib = L.lib()
     need = int(lib.seeme_path_select_workspace_bytes(W, K))
-    ws = _workspace(dev, need)
+    ws = _WS.get(need, dev)
     path = torch.empty(max(W, 0), device=dev, dtype=torch.int32)
     seam = torch.empty(max(W - 1, 0), device=dev, dtype=torch.float32)
     total = torch.empty(1, device=dev, dtype=torch.float32)
-    L.check(lib.seeme_path_select(cost.data_ptr(), L.ptr(unary), W, K, path.data_ptr(), seam.data_ptr(), total.data_ptr(), ws.data_ptr(),
-                                  need if ws_bytes is None else ws_bytes, L.current_stream()), "seeme_path_select")
+    L.call("seeme_path_select", cost.data_ptr(), L.ptr(unary), W, K, path.data_ptr(), seam.data_ptr(), total.data_ptr(), ws.data_ptr(),
+           need if ws_bytes is None else ws_bytes, L.current_stream())
     return {"path": path.long(), "seam_cost": seam, "path_cost": total[0]}
 
 
@@ -376,8 +367,8 @@ def stitch_windows_hip(feats, overlap: int, n_frames: int, layout: int) -> torch
         raise L.SeemeError(f"stitch_windows: features are {tuple(feats.shape)}: expected [W,T,F]")
     W, T, F = (int(n) for n in feats.shape)
     out = torch.empty(max(int(n_frames), 0), F, device=feats.device, dtype=torch.float32)
-    L.check(L.lib().seeme_stitch_windows(feats.contiguous().data_ptr(), W, T, int(overlap), int(n_frames), F, int(layout), out.data_ptr(),
-                                         L.current_stream()), "seeme_stitch_windows")
+    L.call("seeme_stitch_windows", feats.contiguous().data_ptr(), W, T, int(overlap), int(n_frames), F, int(layout), out.data_ptr(),
+           L.current_stream())
     return out
 
 
@@ -398,13 +389,13 @@ def _launch_scene_views(verts, M, P, ws=None, ws_bytes=None, out=None) -> Dict[s
     lib = L.lib()
     need = int(lib.seeme_scene_views_workspace_bytes(N, W, P))
     if ws is None:
-        ws = _workspace(dev, need)
+        ws = _WS.get(need, dev)
     if out is None:
         out = (torch.empty(W, max(P, 0), 3, device=dev, dtype=torch.float32), torch.empty(W, max(P, 0), device=dev, dtype=torch.int32),
                torch.empty(W, device=dev, dtype=torch.int32))
     cloud, index, count = out
-    L.check(lib.seeme_scene_views(verts.data_ptr(), M.data_ptr(), N, W, P, cloud.data_ptr(), index.data_ptr(), count.data_ptr(),
-                                  ws.data_ptr(), need if ws_bytes is None else ws_bytes, L.current_stream()), "seeme_scene_views")
+    L.call("seeme_scene_views", verts.data_ptr(), M.data_ptr(), N, W, P, cloud.data_ptr(), index.data_ptr(), count.data_ptr(),
+           ws.data_ptr(), need if ws_bytes is None else ws_bytes, L.current_stream())
     return {"cloud": cloud, "index": index, "count": count}
 
 

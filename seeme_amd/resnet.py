@@ -123,7 +123,7 @@ class ResNet50(nn.Module):
         for p in self.parameters():
             p.requires_grad = False
         self._wcache = None
-        self._ws = None
+        self._ws = L.Workspace(per_stream=False)
 
     def train(self, mode: bool = True):
         return super().train(False)
@@ -188,8 +188,7 @@ class ResNet50(nn.Module):
         need = L.lib().seeme_resnet50_workspace_bytes(B, prec)
         if need == 0:
             raise L.SeemeError(f"ResNet50: batch size {B} is outside 1..1024")
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = self._ws.get(need, dev)
         w = self._weights()
         if taps is not None:
             dt = torch.bfloat16 if self.precision == "bf16" else torch.float32
@@ -198,8 +197,8 @@ class ResNet50(nn.Module):
             for i, t in enumerate(bufs):
                 w.tap[i] = t.data_ptr()
             taps.extend(bufs)
-        L.check(L.lib().seeme_resnet50_encode(C.byref(w), images.data_ptr(), fmt, B, out.data_ptr(), self._ws.data_ptr(),
-                                              self._ws.numel(), L.current_stream()), "seeme_resnet50_encode")
+        L.call("seeme_resnet50_encode", C.byref(w), images.data_ptr(), fmt, B, out.data_ptr(), ws.data_ptr(), ws.numel(),
+               L.current_stream())
         return out
 
     def forward(self, images: torch.Tensor) -> torch.Tensor:
@@ -239,8 +238,7 @@ def conv2d_nhwc(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, strid
         residual = residual.contiguous()
         if residual.shape != y.shape or residual.dtype != dt:
             raise L.SeemeError("conv2d_nhwc: the residual must have the output's shape and dtype")
-    L.check(L.lib().seeme_resnet_conv(C.byref(c), code, x.data_ptr(), B, H, W, L.ptr(residual), int(relu), y.data_ptr(),
-                                      L.current_stream()), "seeme_resnet_conv")
+    L.call("seeme_resnet_conv", C.byref(c), code, x.data_ptr(), B, H, W, L.ptr(residual), int(relu), y.data_ptr(), L.current_stream())
     return y
 
 
@@ -256,8 +254,7 @@ def stem_pack(images: torch.Tensor, precision: str = "fp32") -> torch.Tensor:
     else:
         raise L.SeemeError("stem_pack: float32 [B,3,H,W] or uint8 [B,H,W,3]")
     y = torch.empty(B, H, W, 16 // torch.empty(0, dtype=dt).element_size(), device=images.device, dtype=dt)
-    L.check(L.lib().seeme_resnet_stem_pack(images.contiguous().data_ptr(), fmt, B, H, W, code, y.data_ptr(), L.current_stream()),
-            "seeme_resnet_stem_pack")
+    L.call("seeme_resnet_stem_pack", images.contiguous().data_ptr(), fmt, B, H, W, code, y.data_ptr(), L.current_stream())
     return y
 
 
@@ -268,6 +265,5 @@ def maxpool_nhwc(x: torch.Tensor, precision: str = "fp32") -> torch.Tensor:
         raise L.SeemeError(f"maxpool_nhwc: x must be a {dt} tensor on the ROCm device")
     B, H, W, Cc = x.shape
     y = torch.empty(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cc, device=x.device, dtype=dt)
-    L.check(L.lib().seeme_resnet_maxpool(code, x.contiguous().data_ptr(), B, H, W, Cc, y.data_ptr(), L.current_stream()),
-            "seeme_resnet_maxpool")
+    L.call("seeme_resnet_maxpool", code, x.contiguous().data_ptr(), B, H, W, Cc, y.data_ptr(), L.current_stream())
     return y

@@ -144,7 +144,7 @@ class SMPL(nn.Module):
         if create_transl:
             self.transl = nn.Parameter(torch.zeros(batch_size, 3, dtype=dtype))
         self._derived = None
-        self._ws = None
+        self._ws = L.Workspace(per_stream=False)
 
     @classmethod
     def synthetic(cls, seed: int = 1234, V: int = 6890, batch_size: int = 1):
@@ -212,13 +212,10 @@ class SMPL(nn.Module):
         ws_ptr, ws_n = 0, 0
         if return_verts:
             verts = torch.empty(M, model.V, 3, device=dev, dtype=torch.float32)
-            need = L.lib().seeme_smpl_workspace_bytes(M)
-            if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            ws_ptr, ws_n = self._ws.data_ptr(), self._ws.numel()
-        rc = L.lib().seeme_smpl_lbs(C.byref(model), betas.data_ptr(), pose.data_ptr(), 0 if pose2rot else 1,
-                                    L.ptr(tr), M, joints.data_ptr(), L.ptr(verts), ws_ptr, ws_n, L.current_stream())
-        L.check(rc, "seeme_smpl_lbs")
+            ws = self._ws.get(L.lib().seeme_smpl_workspace_bytes(M), dev)
+            ws_ptr, ws_n = ws.data_ptr(), ws.numel()
+        L.call("seeme_smpl_lbs", C.byref(model), betas.data_ptr(), pose.data_ptr(), 0 if pose2rot else 1, L.ptr(tr), M,
+               joints.data_ptr(), L.ptr(verts), ws_ptr, ws_n, L.current_stream())
         return SimpleNamespace(vertices=verts, joints=joints, betas=betas, body_pose=body_pose,
                                global_orient=global_orient, full_pose=pose if return_full_pose else None)
 
@@ -236,8 +233,8 @@ class _JointsAA(torch.autograd.Function):
         tr = None if transl is None else transl.to(torch.float32).contiguous()
         joints = torch.empty(M, 45, 3, device=pose.device, dtype=torch.float32)
         model = smpl._model()
-        L.check(L.lib().seeme_smpl_lbs(C.byref(model), betas.data_ptr(), pose.data_ptr(), 0, L.ptr(tr), M, joints.data_ptr(), 0, 0, 0,
-                                       L.current_stream()), "seeme_smpl_lbs")
+        L.call("seeme_smpl_lbs", C.byref(model), betas.data_ptr(), pose.data_ptr(), 0, L.ptr(tr), M, joints.data_ptr(), 0, 0, 0,
+               L.current_stream())
         ctx.smpl, ctx.has_tr = smpl, tr is not None
         ctx.save_for_backward(betas, pose)
         return joints[:, :24]
@@ -250,8 +247,8 @@ class _JointsAA(torch.autograd.Function):
         dpose = torch.empty_like(pose)
         dtr = torch.empty(M, 3, device=pose.device, dtype=torch.float32) if ctx.has_tr else None
         model = ctx.smpl._model()
-        L.check(L.lib().seeme_smpl_joints_backward(C.byref(model), betas.data_ptr(), pose.data_ptr(), dj.data_ptr(), 24, dpose.data_ptr(),
-                                                    L.ptr(dtr), M, L.current_stream()), "seeme_smpl_joints_backward")
+        L.call("seeme_smpl_joints_backward", C.byref(model), betas.data_ptr(), pose.data_ptr(), dj.data_ptr(), 24, dpose.data_ptr(),
+               L.ptr(dtr), M, L.current_stream())
         return None, None, dpose, dtr
 
 
@@ -278,8 +275,8 @@ class _JointsRot6d(torch.autograd.Function):
         tr = None if transl is None else transl.to(torch.float32).reshape(M, 3).contiguous()
         joints = torch.empty(M, 24, 3, device=r6.device, dtype=torch.float32)
         model = smpl._model()
-        L.check(L.lib().seeme_smpl_joints_rot6d(C.byref(model), L.ptr(betas), r6.data_ptr(), order, L.ptr(tr), M, joints.data_ptr(),
-                                                L.current_stream()), "seeme_smpl_joints_rot6d")
+        L.call("seeme_smpl_joints_rot6d", C.byref(model), L.ptr(betas), r6.data_ptr(), order, L.ptr(tr), M, joints.data_ptr(),
+               L.current_stream())
         ctx.smpl, ctx.has_tr, ctx.has_betas, ctx.order = smpl, tr is not None, betas is not None, order
         ctx.save_for_backward(r6, *([betas] if betas is not None else []))
         return joints
@@ -293,9 +290,8 @@ class _JointsRot6d(torch.autograd.Function):
         dr6 = torch.empty_like(r6)
         dtr = torch.empty(M, 3, device=r6.device, dtype=torch.float32) if ctx.has_tr else None
         model = ctx.smpl._model()
-        L.check(L.lib().seeme_smpl_joints_rot6d_backward(C.byref(model), L.ptr(betas), r6.data_ptr(), ctx.order, dj.data_ptr(), 24,
-                                                         dr6.data_ptr(), L.ptr(dtr), M, L.current_stream()),
-                "seeme_smpl_joints_rot6d_backward")
+        L.call("seeme_smpl_joints_rot6d_backward", C.byref(model), L.ptr(betas), r6.data_ptr(), ctx.order, dj.data_ptr(), 24,
+               dr6.data_ptr(), L.ptr(dtr), M, L.current_stream())
         return None, None, dr6, dtr, None
 
 

@@ -50,7 +50,7 @@ class _Group:
         self.n, self.tiles = len(probs), t0
 
     def launch(self):
-        L.check(L.lib().seeme_grouped_gemm(self.dev.data_ptr(), self.n, self.tiles, L.current_stream()), "seeme_grouped_gemm")
+        L.call("seeme_grouped_gemm", self.dev.data_ptr(), self.n, self.tiles, L.current_stream())
 
 
 def _prob(a, b, seg_len, a_ks, b_ks, a_rs, b_cs, c, ldc, M, N, *, a_pro=0, a_p=(0, 0), b_pro=0, b_p=(0, 0), bias=0, epi=0,
@@ -315,9 +315,9 @@ class Stage2Glue:
             a.eps_c, a.slot_c, a.cond = eps_c.data_ptr(), plan.slot_c, plan.cond.data_ptr()
         a.noise, a.timesteps, a.acp, a.freq, a.flip_sin_to_cos = noise.data_ptr(), timesteps.data_ptr(), self.acp.data_ptr(), self.freq.data_ptr(), self.flip
         a.latents, a.noisy, a.tfeat = plan.latents.data_ptr(), plan.noisy.data_ptr(), plan.tfeat.data_ptr()
-        L.check(L.lib().seeme_glue_rows(C.byref(a), st), "seeme_glue_rows")
+        L.call("seeme_glue_rows", C.byref(a), st)
         plan.g_l0.launch()
-        L.check(L.lib().seeme_glue_ln(plan.cond.data_ptr(), plan.xhat.data_ptr(), plan.rstd.data_ptr(), plan.M, st), "seeme_glue_ln")
+        L.call("seeme_glue_ln", plan.cond.data_ptr(), plan.xhat.data_ptr(), plan.rstd.data_ptr(), plan.M, st)
         plan.g_l1.launch()
         plan.g_l2.launch()
         pack = self.pack
@@ -330,7 +330,7 @@ class Stage2Glue:
         plan.masks, plan.drop_scale = draw_dropout_masks(self.den, B, out=plan.drop)
         s.drop, s.drop_scale = L.ptr(plan.masks), plan.drop_scale
         s.xcds = L.default_xcds(B)
-        L.check(L.lib().seeme_denoiser_sample(C.byref(pack.w), C.byref(s), st), "seeme_denoiser_sample")
+        L.call("seeme_denoiser_sample", C.byref(pack.w), C.byref(s), st)
         plan.busy = True
         plan._keep = (dist, eps_z, eps_c, noise, timesteps)
         return plan
@@ -339,14 +339,13 @@ class Stage2Glue:
         pack, st = self.pack, L.current_stream()
         B, N = plan.B, plan.N
         plan.gout.zero_()
-        L.check(L.lib().seeme_denoiser_backward_drop(C.byref(pack.w), pack.img_b.data_ptr(), B, N, plan.save.data_ptr(), plan.ctab.data_ptr(),
-                                                      plan.ttab.data_ptr(), plan.trow.data_ptr(), dout.contiguous().data_ptr(),
-                                                      plan.gout.data_ptr(), plan.dctab.data_ptr(), plan.dttab.data_ptr(),
-                                                      L.ptr(plan.masks), plan.drop_scale, L.default_xcds(B), st), "seeme_denoiser_backward")
+        L.call("seeme_denoiser_backward_drop", C.byref(pack.w), pack.img_b.data_ptr(), B, N, plan.save.data_ptr(), plan.ctab.data_ptr(),
+               plan.ttab.data_ptr(), plan.trow.data_ptr(), dout.contiguous().data_ptr(), plan.gout.data_ptr(), plan.dctab.data_ptr(),
+               plan.dttab.data_ptr(), L.ptr(plan.masks), plan.drop_scale, L.default_xcds(B), st)
         pack.reduce_into_grads(plan.gout)            # chain weights (overwrites its block of the bucket) -- BEFORE the accumulations below
         plan.bind_grads(self)
         plan.g_b0.launch()
-        L.check(L.lib().seeme_glue_mid(C.byref(plan.mid), st), "seeme_glue_mid")
+        L.call("seeme_glue_mid", C.byref(plan.mid), st)
         plan.g_b2.launch()
         plan.g_b3.launch()
         plan.busy = False

@@ -73,8 +73,8 @@ class _Ops:
         when the shape allows (M, N multiples of 128, K of 32), else a problem of the grouped GEMM."""
         if M % 128 == 0 and N % 128 == 0 and K % 32 == 0 and lda % 4 == 0 and ldb % 4 == 0 and A % 16 == 0 and B % 16 == 0 \
                 and os.environ.get("SEEME_GEMM128", "1") != "0":
-            self.ops.append(lambda: L.check(L.lib().seeme_gemm128(A, lda, B, ldb, 1 if nt else 0, Cp, ldc, M, N, K, bias, addend, add_ld,
-                                                                   L.current_stream()), "seeme_gemm128"))
+            self.ops.append(lambda: L.call("seeme_gemm128", A, lda, B, ldb, 1 if nt else 0, Cp, ldc, M, N, K, bias, addend, add_ld,
+                                           L.current_stream()))
         elif nt:
             self.gemm(_gemm_fwd([A], lda, B, ldb, [K], bias, Cp, ldc, M, N, addend=addend, add_ld=add_ld))
         else:
@@ -85,8 +85,7 @@ class _Ops:
         a multiple of 128 x 128, else a split reduction of the grouped GEMM (one member per sequence)."""
         if Nout % 128 == 0 and Kin % 128 == 0 and ldy % 4 == 0 and ldx % 4 == 0 and dy % 16 == 0 and x % 16 == 0 \
                 and os.environ.get("SEEME_GEMM128", "1") != "0":
-            self.ops.append(lambda: L.check(L.lib().seeme_wgrad128(dy, ldy, x, ldx, B * S, Nout, Kin, g, ldg, gbias, L.current_stream()),
-                                            "seeme_wgrad128"))
+            self.ops.append(lambda: L.call("seeme_wgrad128", dy, ldy, x, ldx, B * S, Nout, Kin, g, ldg, gbias, L.current_stream()))
         else:
             self.gemm(_gemm_wgrad(dy, ldy, x, ldx, S, B, g, ldg, Nout, Kin, gbias))
 
@@ -94,16 +93,16 @@ class _Ops:
         a = L.VtLn()
         a.sub, a.res, a.gamma, a.beta, a.y, a.xhat, a.rstd = sub, res, P(norm.weight), P(norm.bias), y, xhat, rstd
         a.M, a.sub_seq_rows, a.eps = M, sub_seq_rows, 1e-5
-        self.ops.append(lambda a=a: L.check(L.lib().seeme_vt_add_ln(C.byref(a), L.current_stream()), "seeme_vt_add_ln"))
+        self.ops.append(lambda a=a: L.call("seeme_vt_add_ln", C.byref(a), L.current_stream()))
 
     def ln_bwd(self, dy, dy2, xhat, rstd, norm, dpre, M):
         a = L.VtLnBwd()
         a.dy, a.dy2, a.xhat, a.rstd, a.gamma, a.dpre = dy, dy2, xhat, rstd, P(norm.weight), dpre
         a.dgamma, a.dbeta, a.M, a.accumulate = P(norm.weight.grad), P(norm.bias.grad), M, 0
-        self.ops.append(lambda a=a: L.check(L.lib().seeme_vt_ln_bwd(C.byref(a), L.current_stream()), "seeme_vt_ln_bwd"))
+        self.ops.append(lambda a=a: L.call("seeme_vt_ln_bwd", C.byref(a), L.current_stream()))
 
     def dropout(self, x, mask, scale, out, n):
-        self.ops.append(lambda: L.check(L.lib().seeme_vt_dropout(x, mask, scale, out, n, L.current_stream()), "seeme_vt_dropout"))
+        self.ops.append(lambda: L.call("seeme_vt_dropout", x, mask, scale, out, n, L.current_stream()))
 
     def call(self, fn):
         self.ops.append(fn)
@@ -186,8 +185,8 @@ class _StackPlan:
         q = P(sv["qkv"])
         ops.gemm(_prob([q], [q + 4 * 256], [256], [1], [1], 768, 768, P(sv["P"]), S, S, S, nbatch=B, bstrides=(S * 768, S * 768, S * S)))
         n_prefix = 0 if self.dec else 2
-        ops.call(lambda p=P(sv["P"]): L.check(L.lib().seeme_vt_softmax_fwd(p, P(self.lengths), B, S, n_prefix, 1.0 / 16.0, L.current_stream()),
-                                              "seeme_vt_softmax_fwd"))
+        ops.call(lambda p=P(sv["P"]): L.call("seeme_vt_softmax_fwd", p, P(self.lengths), B, S, n_prefix, 1.0 / 16.0,
+                                             L.current_stream()))
         dr, ds = self.drop > 0, self.dscale
         pv = P(sv["P"])
         if dr:                                                   # attention-weight dropout of nn.MultiheadAttention
@@ -207,8 +206,8 @@ class _StackPlan:
                                P(sv["vc"]), 256, B, 256))
             if dr:       # cv = W_o v without the bias; per row (w[b,s] cv[b] + b_o) * dropout2 mask
                 ops.gemm(_gemm_fwd([P(sv["vc"])], 256, P(ca.out_proj.weight), 256, [256], 0, P(sv["cv"]), 256, B, 256))
-                ops.call(lambda: L.check(L.lib().seeme_vt_cross_rows(P(sv["cv"]), P(ca.out_proj.bias), P(sv["mw"]), P(sv["mc"]), ds, B, S,
-                                                                      P(self.tmp), L.current_stream()), "seeme_vt_cross_rows"))
+                ops.call(lambda: L.call("seeme_vt_cross_rows", P(sv["cv"]), P(ca.out_proj.bias), P(sv["mw"]), P(sv["mc"]), ds, B, S,
+                                        P(self.tmp), L.current_stream()))
                 ops.add_ln(P(self.tmp), x1, lp.norm2, P(sv["x1b"]), P(sv["xh1b"]), P(sv["rs1b"]), M)
             else:
                 ops.gemm(_gemm_fwd([P(sv["vc"])], 256, P(ca.out_proj.weight), 256, [256], P(ca.out_proj.bias), P(sv["cv"]), 256, B, 256))
@@ -216,7 +215,7 @@ class _StackPlan:
             x1 = P(sv["x1b"])
             n_ffn = lp.norm3
         ops.plain(x1, 256, P(lp.linear1.weight), 256, True, P(sv["hpre"]), 128, M, 128, 256, bias=P(lp.linear1.bias))
-        ops.call(lambda a=P(sv["hpre"]), o=P(sv["h"]): L.check(L.lib().seeme_vt_gelu(a, 0, o, M * 128, L.current_stream()), "seeme_vt_gelu"))
+        ops.call(lambda a=P(sv["hpre"]), o=P(sv["h"]): L.call("seeme_vt_gelu", a, 0, o, M * 128, L.current_stream()))
         if dr:
             ops.dropout(P(sv["h"]), P(sv["mh"]), ds, P(sv["h"]), M * 128)               # dropout inside the FFN
         ops.plain(P(sv["h"]), 128, P(lp.linear2.weight), 128, True, P(self.tmp), 256, M, 256, 128, bias=P(lp.linear2.bias))
@@ -275,7 +274,7 @@ class _StackPlan:
         ops.wgrad(g2, 256, P(sv["h"]), 128, S, B, G(lp.linear2.weight), 128, 256, 128, G(lp.linear2.bias))
         if dr:
             ops.dropout(P(self.dh), P(sv["mh"]), ds, P(self.dh), M * 128)
-        ops.call(lambda: L.check(L.lib().seeme_vt_gelu(P(sv["hpre"]), P(self.dh), P(self.dhpre), M * 128, L.current_stream()), "seeme_vt_gelu"))
+        ops.call(lambda: L.call("seeme_vt_gelu", P(sv["hpre"]), P(self.dh), P(self.dhpre), M * 128, L.current_stream()))
         ops.plain(P(self.dhpre), 128, P(lp.linear1.weight), 256, False, P(self.DX1), 256, M, 256, 128, addend=P(self.G2), add_ld=256)
         ops.wgrad(P(self.dhpre), 128, x1, 256, S, B, G(lp.linear1.weight), 256, 128, 256, G(lp.linear1.bias))
         d_x1 = P(self.DX1)
@@ -288,10 +287,9 @@ class _StackPlan:
                 def bias_grad(ca=ca):
                     ca.out_proj.bias.grad += self.Gm.sum(0)
                 ops.call(bias_grad)
-                ops.call(lambda: L.check(L.lib().seeme_vt_seq_sum(P(self.Gm), P(self.dcv), B, S, 0, P(sv["mw"]), ds, L.current_stream()),
-                                         "seeme_vt_seq_sum"))
+                ops.call(lambda: L.call("seeme_vt_seq_sum", P(self.Gm), P(self.dcv), B, S, 0, P(sv["mw"]), ds, L.current_stream()))
             else:
-                ops.call(lambda: L.check(L.lib().seeme_vt_seq_sum(P(self.G1b), P(self.dcv), B, S, 0, 0, 1.0, L.current_stream()), "seeme_vt_seq_sum"))
+                ops.call(lambda: L.call("seeme_vt_seq_sum", P(self.G1b), P(self.dcv), B, S, 0, 0, 1.0, L.current_stream()))
             ops.gemm(_gemm_dgrad(P(self.dcv), 256, P(ca.out_proj.weight), 256, 256, 256, P(self.dvc), 256, B))
             ops.gemm(_gemm_dgrad(P(self.dvc), 256, P(ca.in_proj_weight) + 4 * 512 * 256, 256, 256, 256, P(self.dz), 256, B, accumulate=1),
                      _gemm_wgrad(P(self.dcv), 256, P(sv["vc"]), 256, B, 1, G(ca.out_proj.weight), 256, 256, 256, 0 if dr else G(ca.out_proj.bias)),
@@ -311,8 +309,7 @@ class _StackPlan:
                  _prob([pv], [P(self.dO)], [S], [S], [256], 1, 1, dq + 4 * 512, 768, S, 256, nbatch=B, bstrides=(S * S, S * 256, S * 768)))
         if dr:
             ops.dropout(P(self.dP), P(sv["mP"]), ds, P(self.dP), B * S * S)
-        ops.call(lambda: L.check(L.lib().seeme_vt_softmax_bwd(P(self.dP), P(sv["P"]), B * S, S, 1.0 / 16.0, L.current_stream()),
-                                 "seeme_vt_softmax_bwd"))
+        ops.call(lambda: L.call("seeme_vt_softmax_bwd", P(self.dP), P(sv["P"]), B * S, S, 1.0 / 16.0, L.current_stream()))
         ops.gemm(_prob([P(self.dP)], [q + 4 * 256], [S], [1], [768], S, 1, dq, 768, S, 256, nbatch=B, bstrides=(S * S, S * 768, S * 768)),
                  _prob([P(self.dP)], [q], [S], [S], [768], 1, 1, dq + 4 * 256, 768, S, 256, nbatch=B, bstrides=(S * S, S * 768, S * 768)))
         ops.plain(dq, 768, P(sa.in_proj_weight), 256, False, out, 256, M, 256, 768, addend=P(self.G1), add_ld=256)

@@ -31,6 +31,53 @@ def test_library_exports_every_declared_symbol():
     assert lib.seeme_version() >= 100
 
 
+def test_signature_table_matches_every_header_prototype():
+    """The whole ctypes table against the whole header: the same names, the same argument counts (a wrong argtypes length would
+    first show up as a wild pointer on the GPU), and every name defined by the built library."""
+    import subprocess
+    from seeme_amd import _lib
+    hdr = open(os.path.join(REPO, "include", "seeme_hip.h")).read()
+    code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
+    protos = re.findall(r"\b(seeme_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", code)
+    assert len(protos) >= 80, "header parse failed"
+    names = [n for n, _ in protos]
+    assert len(set(names)) == len(names)
+    assert set(names) == set(re.findall(r"\b(seeme_[a-z_0-9]+)\s*\(", code)), "a prototype the parser could not read"
+    for name, args in protos:
+        assert name in _lib._SIGNATURES, f"{name} is declared in include/seeme_hip.h but has no ctypes signature"
+        n = 0 if args.strip() in ("", "void") else args.count(",") + 1
+        assert len(_lib._SIGNATURES[name][1]) == n, f"{name}: the header takes {n} arguments, argtypes has {len(_lib._SIGNATURES[name][1])}"
+    assert set(_lib._SIGNATURES) <= set(names), f"not in the header: {sorted(set(_lib._SIGNATURES) - set(names))}"
+    _lib.lib()
+    nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    defined = {line.split()[-1] for line in nm.splitlines() if line.split()}
+    assert set(names) <= defined, f"not defined by the library: {sorted(set(names) - defined)}"
+
+
+def test_call_labels_a_failure_with_the_entry_point():
+    from seeme_amd import _lib
+    with pytest.raises(_lib.SeemeError) as e:      # F = 0: the argument check comes before any device work
+        _lib.call("seeme_pa_mpjpe_frames", 16, 16, 16, 0, 16, 0)
+    assert "seeme_pa_mpjpe_frames" in str(e.value) and "F must" in str(e.value)
+
+
+def test_workspace_grows_only_and_holds_one_buffer_per_key():
+    from seeme_amd import _lib
+    cpu = torch.device("cpu")
+    w = _lib.Workspace(per_stream=False)
+    a = w.get(100, cpu)
+    assert a.dtype == torch.uint8 and a.numel() >= 100
+    assert w.get(50, cpu) is a
+    b = w.get(200, cpu)
+    assert b is not a and b.numel() >= 200
+    assert len(w.cached()) == 1 and w.cached()[0] is b
+    assert w.get(0, cpu) is b
+    w.fill_(0xA5)
+    assert bool((b == 0xA5).all())
+    assert _lib.Workspace(per_stream=False).get(0, cpu).numel() >= 16
+    assert _lib.Workspace(per_stream=True).get(0, cpu).numel() >= 16          # no stream on the CPU: keyed by the device alone
+
+
 def test_pointnet_bf16_struct_mirrors_header():
     """SeemePointnetBf16 holds nothing but pointers, so member names, order and array lengths are its whole layout: the
     ctypes mirror has to repeat the header exactly (a mismatch would first show up as a wild pointer on the GPU)."""
