@@ -605,6 +605,38 @@ size_t seeme_hyp_pairdist_workspace_bytes(int B, int K, int T);   /* 0 for bad s
 int seeme_hyp_pairdist(const float* jts_pred, const int32_t* lengths, int B, int K, int T, float* dist, int32_t* medoid,
                        void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ interpersonal distance and mutual gaze (csrc/social_metrics.hip)
+ * How the wearer stands to the interactee, for the reference body (what an evaluation is binned by) and for each of K hypotheses
+ * (whether a hypothesis reproduces the interaction).  All inputs fp32, 16-byte aligned, in ONE coordinate frame per sequence: there is
+ * no alignment of any kind, the relative placement of the two people is the thing measured.
+ *   jts_pred [B,K,T,24,3] joints of the K hypotheses      quat_pred [B,K,T,4] their global orientation, (w,x,y,z)
+ *   jts_ref  [B,T,24,3]   the wearer's reference joints   quat_ref  [B,T,4]   the reference's global orientation
+ *   jts_int  [B,T,24,3]   the interactee's joints         quat_int  [B,T,4]   the interactee's global orientation
+ *   lengths  [B] int32; n = clamp(len, 0, T) valid frames; every mean below runs over the frames t < n; n = 0 gives zeros.
+ * Per frame, for a body x with orientation q:
+ *   d(x) = |x[0] - int[0]|                                          pelvis-to-pelvis distance
+ *   c(x) = min over the 24 x 24 joint pairs of |x[i] - int[j]|      closest approach
+ *   g(q) = third column of the rotation matrix of q, q normalised as EgoMetrics.quat_to_rotmat does (q sqrt(2 / |q|^2)); a degenerate
+ *          quaternion (|q|^2 < 1e-15) is the identity, g = (0,0,1)
+ *   a(q) = min(atan2(|g(q) x g(q_int)|, g(q) . g(q_int)) 180/pi, 180), degrees in [0, 180].  This is the reference's arccos of the
+ *          normalised dot product (mld/models/metrics/compute.py:31) in the form that stays accurate at 0 and 180 degrees, where the
+ *          arccos loses half its digits.  The products of the cross product are rounded one by one, so parallel directions give
+ *          exactly 0 and antiparallel ones exactly 180.
+ * per_seq [3,B], from the reference body alone (they do not depend on any prediction):
+ *   PERSON_DIST = 1000 mean d(ref) (mm), CLOSEST_DIST_REF = 1000 mean c(ref) (mm), GAZE_ANGLE_REF = mean a(q_ref) (degrees)
+ * per_hyp [5,B,K]:
+ *   PERSON_DIST_ERROR = 1000 mean |d(pred_k) - d(ref)|, CLOSEST_DIST = 1000 mean c(pred_k),
+ *   CLOSEST_DIST_ERROR = 1000 mean |c(pred_k) - c(ref)|, GAZE_ANGLE = mean a(q_pred_k), GAZE_ANGLE_ERROR = mean |a(q_pred_k) - a(q_ref)|
+ * (a hypothesis whose quaternions equal the reference's bit for bit has a GAZE_ANGLE_ERROR of exactly 0).
+ * 1 <= K <= 32, 1 <= B <= 65535, T >= 1.  One workgroup per (sequence, chunk of SEEME_SOCIAL_FRAME_CHUNK frames) writes partial sums
+ * to the workspace (4-byte aligned), a second launch adds them in chunk order.  Frames past n are never read.  No atomics, no
+ * allocation, no synchronisation: bitwise reproducible, and a sequence's values do not depend on B or on the other sequences. */
+#define SEEME_SOCIAL_FRAME_CHUNK 8
+size_t seeme_social_metrics_workspace_bytes(int B, int K, int T);   /* 0 for bad sizes */
+int seeme_social_metrics(const float* jts_pred, const float* jts_ref, const float* jts_int, const float* quat_pred,
+                         const float* quat_ref, const float* quat_int, const int32_t* lengths, int B, int K, int T,
+                         float* per_hyp, float* per_seq, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ a whole recording from overlapping windows (csrc/recording.hip)
  * A recording of n_frames frames is cut into W windows of T frames that start S = T - O frames apart, 0 <= O and 2*O <= T (no frame
  * lies in more than two windows): W = 1 for n_frames <= T, else ceil((n_frames - T) / S) + 1; window w starts at w*S and has

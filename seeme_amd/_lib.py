@@ -225,6 +225,8 @@ _SIGNATURES = {
     "seeme_hyp_metrics": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, C.c_int, fp, fp, fp, C.c_size_t, fp]),
     "seeme_hyp_pairdist_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "seeme_hyp_pairdist": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, fp, fp, fp, C.c_size_t, fp]),
+    "seeme_social_metrics_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "seeme_social_metrics": (C.c_int, [fp, fp, fp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, fp, fp, fp, C.c_size_t, fp]),
     "seeme_overlap_cost_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "seeme_overlap_cost": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, C.c_size_t, fp]),
     "seeme_path_select_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),

@@ -62,6 +62,8 @@ def build_parser(phase: str) -> argparse.ArgumentParser:
                    help="set TEST.MESH_METRICS: PA-MPJPE, V2V and body-scene contact per hypothesis (seeme_amd/mesh_metrics.py)")
     s.add_argument("--collision_metrics", action="store_true",
                    help="set TEST.COLLISION_METRICS: share of the scene cloud inside the body per hypothesis (needs a 'scene' condition)")
+    s.add_argument("--social_metrics", action="store_true",
+                   help="set TEST.SOCIAL_METRICS: the errors by interpersonal distance and mutual gaze (seeme_amd/social_metrics.py)")
     t = p.add_argument_group("training loop (seeme_amd/optim.py, INTEGRATION.md J)")
     t.add_argument("--ema_decay", type=float, default=None, help="override TRAIN.EMA_DECAY (0 = no EMA of the weights)")
     t.add_argument("--grad_clip", type=float, default=None, help="override TRAIN.GRAD_CLIP_NORM (0 = no gradient-norm clipping)")
@@ -85,6 +87,8 @@ def load_cfg(args, phase: str):
         cfg.TEST.MESH_METRICS = True
     if getattr(args, "collision_metrics", False):
         cfg.TEST.COLLISION_METRICS = True
+    if getattr(args, "social_metrics", False):
+        cfg.TEST.SOCIAL_METRICS = True
     if getattr(args, "ema_decay", None) is not None:
         cfg.TRAIN.EMA_DECAY = args.ema_decay
     if getattr(args, "grad_clip", None) is not None:
@@ -398,6 +402,7 @@ def test_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=None
         model.MeshMetric.reset()
         model.CollMetric.reset()
         model.SelMetric.reset()
+        model.SocialMetric.reset()
         t0 = time.perf_counter()
         with torch.no_grad():
             if hasattr(dm, "iterate"):  # files: ONE pass over the test split, every sequence exactly once over the ranks (test.py:115-133)
@@ -423,6 +428,8 @@ def test_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=None
             metrics.update(model.CollMetric.compute(D.reduce_sums(model.CollMetric.sums().to(dev)).cpu()))
         if model.hyp_select == "medoid" and model.num_hypotheses > 1:    # the errors of the label-free choice among the K draws
             metrics.update(model.SelMetric.compute(D.reduce_sums(model.SelMetric.sums().to(dev)).cpu()))
+        if model.social_metrics:        # MPJPE by interpersonal distance and by mutual gaze, and how well the interaction is reproduced
+            metrics.update(model.SocialMetric.compute(D.reduce_sums(model.SocialMetric.sums().to(dev)).cpu(), model.num_hypotheses))
         log.info("Replication %d: %s", rep, json.dumps({k: round(v, 4) for k, v in metrics.items()}))
         for k, v in metrics.items():
             all_metrics.setdefault(k, []).append(float(v))

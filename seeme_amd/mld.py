@@ -51,6 +51,7 @@ from .resnet import ResNet50
 from .respointnet import ResnetPointnet
 from .shapes import motion_layout
 from .smpl import SMPL
+from .social_metrics import DEFAULT_DIST_EDGES, DEFAULT_GAZE_EDGES, SocialMetrics, check_edges, social_metrics_hip
 
 
 IMAGE_FEAT_DIM = 2048          # pooled ResNet-50 feature of proscene.encode_image (prohmr_scene.py:99-100, BACKBONE.OUT_CHANNELS)
@@ -399,6 +400,23 @@ class MLD(nn.Module):
             raise ValueError(f"TEST.COLLISION_METRICS must be true or false, got {self.collision_metrics!r}")
         if self.collision_metrics and "scene" not in self.condition:
             raise ValueError("TEST.COLLISION_METRICS needs the scene cloud, and model.condition has no 'scene': it would report nothing")
+        # the evaluation by interpersonal distance and mutual gaze (seeme_amd/social_metrics.py): off = today's result, key for key
+        self.social_metrics = cfg.TEST.get("SOCIAL_METRICS", False)
+        if not isinstance(self.social_metrics, bool):
+            raise ValueError(f"TEST.SOCIAL_METRICS must be true or false, got {self.social_metrics!r}")
+        self.social_dist_edges = check_edges(cfg.TEST.get("SOCIAL_DIST_EDGES", list(DEFAULT_DIST_EDGES)), "TEST.SOCIAL_DIST_EDGES")
+        self.social_gaze_edges = check_edges(cfg.TEST.get("SOCIAL_GAZE_EDGES", list(DEFAULT_GAZE_EDGES)), "TEST.SOCIAL_GAZE_EDGES",
+                                             0.0, 180.0)
+        if self.social_metrics:
+            if self.data_type != "angle":
+                raise ValueError(f"TEST.SOCIAL_METRICS needs DATA_TYPE 'angle' (got {self.data_type!r}): there are no orientation "
+                                 "quaternions otherwise")
+            if not self.predict_transl:
+                raise ValueError("TEST.SOCIAL_METRICS needs TRAIN.ABLATION.PREDICT_TRANSL: without the translation in the features the "
+                                 "two bodies are not in one frame")
+            if self.estimate != "wearer":
+                raise ValueError(f"TEST.SOCIAL_METRICS needs ESTIMATE 'wearer' (got {self.estimate!r}): the distances and angles are the "
+                                 "wearer's to the interactee")
         # training-loop options (seeme_amd/optim.py): EMA of the trainable weights and clipping of the global gradient norm; 0 = off
         from .optim import check_options
         self.ema_decay, self.grad_clip_norm = check_options(cfg.TRAIN.get("EMA_DECAY", 0.0), cfg.TRAIN.get("GRAD_CLIP_NORM", 0.0),
@@ -469,6 +487,7 @@ class MLD(nn.Module):
         self.MeshMetric = MeshMetrics()
         self.CollMetric = CollisionMetrics()
         self.SelMetric = SelectionMetrics()
+        self.SocialMetric = SocialMetrics(self.social_dist_edges, self.social_gaze_edges)
         self.do_classifier_free_guidance = self.guidance_scale > 1.0
         self.renorm = datamodule.renorm if datamodule is not None else (lambda x: x)
         self.times: List[float] = []
@@ -994,6 +1013,9 @@ class MLD(nn.Module):
         if want_vertices:
             rs["vertices_ref"], rs["vertices_rst"] = out_ref[1], out_rst[1]
         self._add_mesh_results(rs, f_rst, f_ref, b_ref, o_rst, lengths, 1, scene)
+        if self.social_metrics:
+            rs["social_metrics"] = social_metrics_hip(joints_rst[:, None], joints_ref, joints_int, rs["orientation_quat_rst"],
+                                                      rs["orientation_quat_ref"], rs["orientation_quat_int"], lengths)
         return rs
 
     def _interactee_gt_joints(self, int_gt, beta, min_len):
@@ -1174,6 +1196,8 @@ class MLD(nn.Module):
               "list_names": {}, "lat_t": pick(z.view(B, K, -1))[None],
               "joints_rst_all": joints_all, "m_rst_all": f_rst.view(B, K, min_len, -1), "lat_t_all": z, "hyp_metrics": hm}
         self._add_mesh_results(rs, f_rst, f_ref, b_ref, o_ref, lengths, K, scene)
+        if self.social_metrics:
+            rs["social_metrics"] = social_metrics_hip(joints_all, joints_ref, joints_int, q_all, q_ref, rs["orientation_quat_int"], lengths)
         if want_vertices:                                                   # meshes of the selected hypothesis only (6890 vertices per frame)
             rs["vertices_ref"] = out_ref[1]
             rs["vertices_rst"] = self._feats_to_joints(f_rst0, b_ref, True, orient=o_ref)[1]
@@ -1338,6 +1362,16 @@ class MLD(nn.Module):
                 self.MeshMetric.update(rs_set["mesh_metrics"], keep)
             if "collision_metrics" in rs_set:                              # TEST.COLLISION_METRICS
                 self.CollMetric.update(rs_set["collision_metrics"])
+            if "social_metrics" in rs_set:                                 # TEST.SOCIAL_METRICS
+                if "hyp_metrics" in rs_set:
+                    hm = rs_set["hyp_metrics"]
+                    mp, root, keep = hm["MPJPE"], hm["ROOT_ERROR"], keep_mask(hm, split, hm["have_quat"])
+                else:                                                      # K = 1: the sequences EgoMetrics.update counts for MPJPE
+                    per = {k: v[:, None] for k, v in EgoMetrics.per_sequence(
+                        rs_set["joints_rst"], rs_set["joints_ref"], rs_set["lengths"], rs_set["orientation_quat_rst"],
+                        rs_set["orientation_quat_ref"]).items()}
+                    mp, root, keep = per["MPJPE"], per["ROOT_ERROR"], keep_mask(per, split, True)
+                self.SocialMetric.update(rs_set["social_metrics"], mp, root, keep)
         if split == "test":
             return rs_set["joints_rst"]
         return loss
