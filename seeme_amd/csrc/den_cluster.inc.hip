@@ -279,19 +279,46 @@ __device__ __forceinline__ void clg_issue(ClRing2& ring, unsigned voff, __amdgpu
 }
 // consume a slot: cl_consume's stage loads (k-block j / TPW, tile j % TPW) for both stored waves, alternating -- two independent accumulator
 // chains per tile index, one fragment read for both; per tile the k-blocks in cl_consume's order
-template <typename WT, int TPW, int J0, int KBOFF>
-__device__ __forceinline__ void clg_consume(const u32x4 (&slot)[2][8], const ClX& x, f32x4 (&acc)[2][TPW]) {
+//
+// The A-operand fragments of a phase are read AHEAD of its first MFMA (clg_frags: NK k-blocks, back to back), not one k-block at a time in
+// front of the MFMAs that use it: only four waves compute in a phase, one per SIMD, so nothing hides an LDS round trip (>= 64 cycles against
+// 2 x 16 of the two MFMAs it feeds) -- phase time followed the number of such trips (D: 8 trips 0.96 k cycles, E: 4 trips 0.57 k, the same 16
+// MFMAs).  LDS returns in order, so the MFMAs of k-block i wait with lgkmcnt(reads behind it), not lgkmcnt(0).
+template <int NK>
+__device__ __forceinline__ void clg_frags(uint4 (&f)[NK], const ClX& x) {
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        f[k] = *reinterpret_cast<const uint4*>(x.base + x.foff + k * x.kbs);
+        if (k == 0) __builtin_amdgcn_sched_barrier(0);        // (k-block 0 first: left to itself the scheduler requests it last in three of six phases)
+    }
+}
+template <typename WT, int TPW, int NK, int K0>      // f[K0 ..]: the 8 / TPW k-blocks of this unit
+__device__ __forceinline__ void clg_consume(const u32x4 (&slot)[2][8], const uint4 (&f)[NK], f32x4 (&acc)[2][TPW]) {
     static_assert(WT::MFMA, "16-bit images only");
-    uint4 a4 = make_uint4(0u, 0u, 0u, 0u);
+    static_assert(K0 + 8 / TPW <= NK, "fragments of the unit");
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        const int j = J0 + i, kb = j / TPW - KBOFF, t = j % TPW;
-        if (i == 0 || t == 0) a4 = *reinterpret_cast<const uint4*>(x.base + x.foff + kb * x.kbs);
+        const int k = K0 + i / TPW, t = i % TPW;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            if constexpr (WT::HALF) acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, a4), __builtin_bit_cast(h16x8, slot[h][i]), acc[h][t], 0, 0, 0);
-            else acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a4), __builtin_bit_cast(bf16x8, slot[h][i]), acc[h][t], 0, 0, 0);
+            if constexpr (WT::HALF) acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, f[k]), __builtin_bit_cast(h16x8, slot[h][i]), acc[h][t], 0, 0, 0);
+            else acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, f[k]), __builtin_bit_cast(bf16x8, slot[h][i]), acc[h][t], 0, 0, 0);
         }
+    }
+}
+// phase A's first k-half (one tile per stored wave): behind the MFMAs of k-block i its fragment register takes k-block i of the NEXT input
+// vector (the skip input), so that the second k-half finds its fragments read as well -- sixteen fragments at once do not fit the registers
+template <typename WT>
+__device__ __forceinline__ void clg_consume_refill(const u32x4 (&slot)[2][8], uint4 (&f)[8], const ClX& xn, f32x4 (&acc)[2][1]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            if constexpr (WT::HALF) acc[h][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, f[i]), __builtin_bit_cast(h16x8, slot[h][i]), acc[h][0], 0, 0, 0);
+            else acc[h][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, f[i]), __builtin_bit_cast(bf16x8, slot[h][i]), acc[h][0], 0, 0, 0);
+        }
+        f[i] = *reinterpret_cast<const uint4*>(xn.base + xn.foff + i * xn.kbs);
+        __builtin_amdgcn_sched_barrier(0);
     }
 }
 // value of the lane's tile: 16-lane group g of a wave writes tile g of acc[stored wave][tile]
@@ -392,6 +419,50 @@ struct ClRow {
     }
 };
 
+// Two wave groups: what the scheduler step reads travels the same way, in the rows that waves 6 and 7 used to drop -- wave 6: the 8 coefficients
+// of THIS step (lanes read coef[step][4 (lane & 1) ..]), wave 7: the sample's row of step noise (when given) -- into COEF | NZ behind the window
+// flags, and every wave reads the table row of the NEXT step (trow) for itself.  They are requested in the X1 window of EVERY layer (no branch
+// around a request; the five windows of a step write the same values, and the step's closing barrier stands between the scheduler's reads and
+// the next step's first window), so the scheduler step finds them in LDS and waits for no global load: before, it issued two dependent pairs
+// of scalar loads behind the stack norm, the noise row was loaded at its use with vmcnt(0) -- draining the weight ring -- and the next row was a
+// scalar load waited for at the top of the layer loop.  Without a scheduler (forward) / without noise the lanes re-read the row they dropped.
+struct ClRowG {
+    float4 r; int t;
+    __device__ __forceinline__ void load(int wave, int lane, const float* __restrict__ tt_row, const float* __restrict__ ca_row, int l,
+                                         const SeemeSampleArgs& A, int b, int step, int step_next) {
+        int z = 0;
+        asm volatile("" : "+v"(z));        // (a lane-dependent address in form: a vector load, counted by vmcnt like the row behind it)
+        t = A.trow[(A.trow_per_sample ? b : step_next) + z];
+        const int j = wave - 1 - (wave > 5 ? 5 : 0);
+        const float* src = (j < 2 ? tt_row + l * 512 + j * 256 : (j < 4 ? tt_row + 2560 + l * 1024 + 512 + (j - 2) * 256 : ca_row)) + 4 * lane;
+        if (wave == 6 && A.sched != SEEME_SCHED_NONE) src = A.coef + (size_t)step * 8 + 4 * (lane & 1);
+        if (wave == 7 && A.noise != nullptr) src = A.noise + ((size_t)step * A.B + b) * 256 + 4 * lane;
+        r = *reinterpret_cast<const float4*>(src);
+    }
+    // one LDS write per wave: rows 0 .. 4 (waves 1 .. 5) | COEF (wave 6: every lane pair writes the same 8 floats) | NZ (wave 7); returns the next step's row
+    __device__ __forceinline__ int store(int wave, int lane, float* __restrict__ rows, float* __restrict__ coef, float* __restrict__ nz) const {
+        float* dst = wave == 6 ? coef + 4 * (lane & 1) : (wave == 7 ? nz + 4 * lane : rows + (wave - 1) * 256 + 4 * lane);
+        *reinterpret_cast<float4*>(dst) = r;
+        return __builtin_amdgcn_readfirstlane(t);
+    }
+};
+
+// One element of scheduler.step as the loop below forms it when the compiler contracts it with the coefficients in scalar-load pairs (c2 | c3,
+// c4 | c5): elements 0 .. 2 of a lane are one chain of fused multiply-adds, element 3 is paired differently -- fma(c2, x0, c3 ep), an unfused
+// c5 x added, then fma(c4, n, .) -- in every kernel of this file and in k_den_cluster_ms.  With the coefficients read from LDS the compiler no
+// longer sees those pairs and would chain element 3 like the others (one ulp in every fourth latent), so the two-wave-group kernels spell
+// the sums out: the same bits as before, and as the eight-wave body they are tested against.  Both divisions are divisions.
+__device__ __forceinline__ float cl_sched_elem(bool e3, float x, float e, float n, float c0, float c1, float c2, float c3, float c4, float c5,
+                                               float clip, float ptype) {
+#pragma clang fp contract(off)
+    float x0, ep;
+    if (ptype == 0.f) { ep = e; x0 = fmaf(-c1, ep, x) / c0; }
+    else              { x0 = e; ep = fmaf(-c0, x0, x) / c1; }
+    if (clip != 0.f) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+    if (e3) return fmaf(c4, n, c5 * x + fmaf(c2, x0, c3 * ep));
+    return fmaf(c4, n, fmaf(c5, x, fmaf(c3, ep, c2 * x0)));
+}
+
 template <int C, bool Q>
 struct ClStage {
     float4 r; int dst, n4;        // ONE piece per wave and phase (Q: k = 0 .. 4 in phases B, C, H, D, F): 4 registers live across a phase
@@ -479,6 +550,8 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
     float* PART = KS + G::S;                     // [256]
     float* RES = PART + 256;                     // [256]  the fp32 residual stream
     int* FLG = reinterpret_cast<int*>(RES + 256);   // [4]
+    float* COEF = RES + 256 + 4;                 // (GRP) [8]   the step's scheduler coefficients (+ 4 spare), see ClRowG
+    float* NZ = COEF + 12;                       // (GRP) [256] the sample's step noise
     constexpr int XZERO = 512 + 512 + 2 * (G::NB > 128 ? G::NB : 128) + 1024;
 
     const __amdgpu_buffer_rsrc_t wg = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ka.wgc), 0, (int)ka.wgc_bytes, 0x00020000);
@@ -533,7 +606,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
     }
     ClRing<WT> ring;
     ClRing2 gr;                                  // (GRP)
-    (void)gr; (void)gvoff; (void)w4;
+    (void)gr; (void)gvoff; (void)w4; (void)COEF; (void)NZ;
     if constexpr (GRP) {
         if (wave < 4) {       // layer 0 has no skip linear; A1 is requested all the same (nowhere), as after every phase F: one count of loads in flight at a layer's start
             clg_issue<0>(gr, gvoff, wg, (unsigned)(c * G::NU + G::U_A) * W::UNIT_BYTES, true, w4 < 2);
@@ -547,13 +620,18 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
     }
     __syncthreads();
     int cur = 0;
+    int row_nx = row;                            // (GRP) table row of the next step, as this wave last read it
+    (void)row_nx;
 
 #pragma unroll 1
     for (int step = 0; step < A.steps; ++step) {
         if (step == 2) DEN_DBG(1);
         if (step == 3) DEN_DBG(2);
         const int step_next = step + 1 < A.steps ? step + 1 : step;
-        const int row_next = A.trow_per_sample ? row : trow_c[step_next];
+        // the table row of the next step: a scalar load here, waited for at the top of the layer loop -- or (GRP) read by every wave for itself
+        // in the X1 windows (ClRowG; row_nx as of layer 3's window when layer 4's asks for it)
+        int row_next = row;
+        if constexpr (!GRP) row_next = A.trow_per_sample ? row : trow_c[step_next];
 #pragma unroll 1
         for (int l = 0; l < SEEME_DEN_NL; ++l) {
             const DenLayerOff* __restrict__ L = &lay->L[l];
@@ -584,7 +662,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
             (void)CA_ADD; (void)v_cnw; (void)v_cnb; (void)v_caq_b; (void)v_csnw; (void)v_csnb; (void)v_cao_b;
             const bool ywave = wave >= 6;
             // the next layer's changing operands: table row of the next step behind the last layer
-            const float* const tt_next = A.ttab + (size_t)(ln == 0 ? row_next : row) * SEEME_TROW;
+            const float* const tt_next = A.ttab + (size_t)(ln == 0 ? (GRP ? row_nx : row_next) : row) * SEEME_TROW;
             const int ca_next = A.trow_per_sample ? 0 : (ln == 0 ? step_next : step);
             ClStage<C, true> nxt;       // (Q)
             (void)nxt; (void)ca_next;
@@ -596,23 +674,25 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
                     // ======== group G1: phases B, D, F; the same barriers as G0 below, which runs A, C, E and the epilogue wave's parts ========
                     __syncthreads();                                                   // A
                     {   // X1 published: the next layer's changing row (oldest load, see ClRow), then unit B
-                        ClRow nrow;
+                        ClRowG nrow;
                         cl_flag_wait(FLG + 1, e1);
-                        nrow.load(wave, lane, tt_next, A.catab + (((size_t)b * ca_R + ca_next) * SEEME_DEN_NL + ln) * 256, ln);
+                        nrow.load(wave, lane, tt_next, A.catab + (((size_t)b * ca_R + ca_next) * SEEME_DEN_NL + ln) * 256, ln, A, b, step, step_next);
                         __builtin_amdgcn_sched_barrier(0);
                         clg_issue<0>(gr, gvoff, wg, bc + (unsigned)G::U_B * W::UNIT_BYTES, true, true);
-                        nrow.store(wave, lane, ROWS + (cur ^ 1) * R::ROWS);
+                        row_nx = nrow.store(wave, lane, ROWS + (cur ^ 1) * R::ROWS, COEF, NZ);
                     }
                     __syncthreads();                                                   // X1
                     {   // B: linear1 + ReLU
                         f32x4 acc[2][1];
+                        uint4 fr[8];
+                        const int j = (w4 + 4 * ((lane >> 4) & 1)) * 16 + col;
+                        clg_frags<8>(fr, xb);
+                        const float bias = v_l1b[j];                                   // ahead of the MFMAs: no LDS round trip behind them
+                        __builtin_amdgcn_sched_barrier(0);
                         cl_zero<1>(acc[0]); cl_zero<1>(acc[1]);
-                        clg_consume<WT, 1, 0, 0>(gr.r[0], xb, acc);
+                        clg_consume<WT, 1, 8, 0>(gr.r[0], fr, acc);
                         cl_pin<1>(acc[0]); cl_pin<1>(acc[1]);
-                        if (lane < 32) {
-                            const int j = (w4 + 4 * (lane >> 4)) * 16 + col;
-                            cl_put1<WT>(XH, j, fmaxf(clg_out<WT, 1>(acc, lane) + v_l1b[j], 0.f));
-                        }
+                        if (lane < 32) cl_put1<WT>(XH, j, fmaxf(clg_out<WT, 1>(acc, lane) + bias, 0.f));
                     }
                     __syncthreads();                                                   // B
                     cl_flag_wait(FLG + 1, e2);                                         // X2 published: D
@@ -622,13 +702,15 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
                     __syncthreads();                                                   // C + X2
                     {   // D: ffn.linear1 + GELU
                         f32x4 acc[2][1];
+                        uint4 fr[8];
+                        const int j = (w4 + 4 * ((lane >> 4) & 1)) * 16 + col;
+                        clg_frags<8>(fr, xa);
+                        const float bias = v_f1b[j];
+                        __builtin_amdgcn_sched_barrier(0);
                         cl_zero<1>(acc[0]); cl_zero<1>(acc[1]);
-                        clg_consume<WT, 1, 0, 0>(gr.r[1], xa, acc);
+                        clg_consume<WT, 1, 8, 0>(gr.r[1], fr, acc);
                         cl_pin<1>(acc[0]); cl_pin<1>(acc[1]);
-                        if (lane < 32) {
-                            const int j = (w4 + 4 * (lane >> 4)) * 16 + col;
-                            cl_put1<WT>(XH, j, fast_gelu(clg_out<WT, 1>(acc, lane) + v_f1b[j]));
-                        }
+                        if (lane < 32) cl_put1<WT>(XH, j, fast_gelu(clg_out<WT, 1>(acc, lane) + bias));
                     }
                     __syncthreads();                                                   // D
                     // F1 in two halves, phase E and the ffn epilogue: the 64 wave-loads of a whole unit take the address path longer than phase E lasts,
@@ -639,13 +721,17 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
                     __syncthreads();                                                   // ffn epilogue
                     {   // F: ffn.proj_out.out_layers + residual; writes the next layer's input
                         f32x4 acc[2][2];
-                        cl_zero<2>(acc[0]); cl_zero<2>(acc[1]);
-                        clg_consume<WT, 2, 0, 0>(gr.r[0], xb, acc);
-                        cl_pin<2>(acc[0]); cl_pin<2>(acc[1]);
-                        clg_consume<WT, 2, W::UL, 0>(gr.r[1], xb, acc);
-                        cl_pin<2>(acc[0]); cl_pin<2>(acc[1]);
+                        uint4 fr[8];
                         const int n = (2 * (w4 + 4 * (lane >> 5)) + ((lane >> 4) & 1)) * 16 + col;
-                        const float xn = RES[n] + clg_out<WT, 2>(acc, lane) + v_fo_b[n];
+                        clg_frags<8>(fr, xb);
+                        const float res = RES[n], bias = v_fo_b[n];                    // (RES: final since norm2, three barriers back)
+                        __builtin_amdgcn_sched_barrier(0);
+                        cl_zero<2>(acc[0]); cl_zero<2>(acc[1]);
+                        clg_consume<WT, 2, 8, 0>(gr.r[0], fr, acc);
+                        cl_pin<2>(acc[0]); cl_pin<2>(acc[1]);
+                        clg_consume<WT, 2, 8, 4>(gr.r[1], fr, acc);
+                        cl_pin<2>(acc[0]); cl_pin<2>(acc[1]);
+                        const float xn = res + clg_out<WT, 2>(acc, lane) + bias;
                         RES[n] = xn;
                         cl_put1<WT>(XA, n, xn);
                         if (l < 2) cl_put1<WT>(SKF + 512 * l, n, xn);
@@ -659,23 +745,27 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
 
             // ================= A: in_proj' (+ folded skip linear), column-split by dims =================
             if constexpr (GRP) {
+                // Fragments of the layer input and the lane's bias go out ahead of the first MFMA, those of the skip input (second k-half: final
+                // since layers 0 / 1; read in every layer, used where the layer has a skip linear) into the registers the first k-half frees.
+                // Lane epilogue: stored wave = tile; waves 0,1: q; 2,3: k; 4,5: v'; 6,7: y -- this wave plays w4 in lanes 0 .. 15 (q or k -> LDS)
+                // and w4 + 4 in lanes 16 .. 31 (v', or y where the layer has a skip linear -> granule): one bias read ahead of the chain, one
+                // add, one store of either kind instead of four nested sections with a read each.  The granule goes first: peers wait for it.
                 f32x4 acc[2][1];
+                uint4 fr[8];
+                const bool hi = (lane & 16) != 0, qv = w4 < 2;
+                const int d = (w4 & 1) * 16 + col;
+                const float* bsrc = hi ? (qv ? v_in_b + 2 * IN_ST : v_skip_b) : (qv ? v_in_b : v_in_b + IN_ST);
+                clg_frags<8>(fr, xa);
+                const float bias = bsrc[d];
+                __builtin_amdgcn_sched_barrier(0);
                 cl_zero<1>(acc[0]); cl_zero<1>(acc[1]);
-                clg_consume<WT, 1, 0, 0>(gr.r[0], xa, acc);
+                clg_consume_refill<WT>(gr.r[0], fr, cl_xin<WT>(SKF + (l == 3 ? 512 : 0), lane), acc);
                 cl_pin<1>(acc[0]); cl_pin<1>(acc[1]);
-                if (skip) {   // second k-half: the skip input (see below)
-                    const ClX xs = cl_xin<WT>(SKF + (l == 3 ? 512 : 0), lane);
-                    clg_consume<WT, 1, W::UL, W::UL>(gr.r[1], xs, acc);
-                }
+                if (skip) clg_consume<WT, 1, 8, 0>(gr.r[1], fr, acc);
                 cl_pin<1>(acc[0]); cl_pin<1>(acc[1]);
-                if (lane < 32) {
-                    const int sw = w4 + 4 * (lane >> 4), d = (sw & 1) * 16 + col;      // stored wave = tile; waves 0,1: q; 2,3: k; 4,5: v'; 6,7: y
-                    const float val = clg_out<WT, 1>(acc, lane);
-                    if (sw < 2) QS[d] = val + v_in_b[d];
-                    else if (sw < 4) KS[d] = val + v_in_b[IN_ST + d];
-                    else if (sw < 6) cl_store_granule(xg + G::G_X1 + c * G::X1_G + d, e1, val + v_in_b[2 * IN_ST + d], local);
-                    else if (skip) cl_store_granule(xg + G::G_X1 + c * G::X1_G + G::S + d, e1, val + v_skip_b[d], local);
-                }
+                const float val = clg_out<WT, 1>(acc, lane) + bias;
+                if (hi && lane < 32 && (qv || skip)) cl_store_granule(xg + G::G_X1 + c * G::X1_G + (qv ? 0 : G::S) + d, e1, val, local);
+                if (lane < 16) (qv ? QS : KS)[d] = val;
             } else {
                 f32x4 acc[G::TA];
                 cl_zero<G::TA>(acc);
@@ -787,9 +877,12 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
                 // the next layer's changing row first: the OLDEST load of the window.  It is stored behind the window's units, in front of the
                 // barrier at which these waves wait out the epilogue wave's sweep and vector algebra anyway: the store's wait is
                 // vmcnt(units requested behind the row) -- it leaves every unit in flight and the row has had the whole exchange to land.
-                ClRow nrow;
+                std::conditional_t<GRP, ClRowG, ClRow> nrow;
                 if constexpr (WIN) cl_flag_wait(FLG + 1, e1);
-                if constexpr (RSD) {
+                if constexpr (GRP) {
+                    nrow.load(wave, lane, tt_next, A.catab + (((size_t)b * ca_R + ca_next) * SEEME_DEN_NL + ln) * 256, ln, A, b, step, step_next);
+                    __builtin_amdgcn_sched_barrier(0);
+                } else if constexpr (RSD) {
                     nrow.load(wave, lane, tt_next, A.catab + (((size_t)b * ca_R + ca_next) * SEEME_DEN_NL + ln) * 256, ln);
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -799,7 +892,8 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
                     cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W1B{});
                     if constexpr (GRP) clg_issue<0>(gr, gvoff, wg, bc + (unsigned)G::U_C * W::UNIT_BYTES, true, true);
                 }
-                if constexpr (RSD) nrow.store(wave, lane, ROWS + (cur ^ 1) * R::ROWS);
+                if constexpr (GRP) row_nx = nrow.store(wave, lane, ROWS + (cur ^ 1) * R::ROWS, COEF, NZ);
+                else if constexpr (RSD) nrow.store(wave, lane, ROWS + (cur ^ 1) * R::ROWS);
             }
             __syncthreads(); DEN_DBG(0);
 
@@ -829,8 +923,11 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
             if constexpr (Q) nxt.load(1, wave, lane, vp, Ln, tt_next, ln, A, b, c, ca_next, ca_R);
             if constexpr (GRP) {
                 f32x4 acc[2][2];
+                uint4 fr[4];
+                clg_frags<4>(fr, xh);
+                __builtin_amdgcn_sched_barrier(0);
                 cl_zero<2>(acc[0]); cl_zero<2>(acc[1]);
-                clg_consume<WT, 2, 0, 0>(gr.r[0], xh, acc);
+                clg_consume<WT, 2, 4, 0>(gr.r[0], fr, acc);
                 cl_pin<2>(acc[0]); cl_pin<2>(acc[1]);
                 cl_store_granule(xg + G::G_X2 + c * 256 + (2 * (w4 + 4 * (lane >> 5)) + ((lane >> 4) & 1)) * 16 + col, e2, clg_out<WT, 2>(acc, lane), local);
             } else {
@@ -1036,8 +1133,11 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
             // ================= E: ffn.linear2 -> LayerNorm, AdaLN, SiLU (replicated) =================
             if constexpr (GRP) {
                 f32x4 acc[2][2];
+                uint4 fr[4];
+                clg_frags<4>(fr, xh);
+                __builtin_amdgcn_sched_barrier(0);
                 cl_zero<2>(acc[0]); cl_zero<2>(acc[1]);
-                clg_consume<WT, 2, 0, 0>(gr.r[1], xh, acc);
+                clg_consume<WT, 2, 4, 0>(gr.r[1], fr, acc);
                 cl_pin<2>(acc[0]); cl_pin<2>(acc[1]);
                 PART[(2 * (w4 + 4 * (lane >> 5)) + ((lane >> 4) & 1)) * 16 + col] = clg_out<WT, 2>(acc, lane);
             } else {
@@ -1092,20 +1192,33 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
                     if (A.sched == SEEME_SCHED_NONE) {
                         st4(KEEP + 4 * lane, e);
                     } else {
-                        const CF32 cf = coef_c + (size_t)step * 8;
-                        const float c0 = cf[0], c1 = cf[1], c2 = cf[2], c3 = cf[3], c4 = cf[4], c5 = cf[5], clip = cf[6], ptype = cf[7];
+                        float c0, c1, c2, c3, c4, c5, clip, ptype;
                         float4 nz = make_float4(0.f, 0.f, 0.f, 0.f);
-                        if (A.noise != nullptr) nz = ld4(A.noise + ((size_t)step * A.B + b) * 256 + 4 * lane);
+                        if constexpr (GRP) {      // in LDS since this step's X1 windows (ClRowG); uniform values back into scalar registers
+                            const float4 k0 = ld4(COEF), k1 = ld4(COEF + 4);
+                            const auto sc = [](float v) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v))); };
+                            c0 = sc(k0.x); c1 = sc(k0.y); c2 = sc(k0.z); c3 = sc(k0.w); c4 = sc(k1.x); c5 = sc(k1.y); clip = sc(k1.z); ptype = sc(k1.w);
+                            if (A.noise != nullptr) nz = ld4(NZ + 4 * lane);
+                        } else {
+                            const CF32 cf = coef_c + (size_t)step * 8;
+                            c0 = cf[0]; c1 = cf[1]; c2 = cf[2]; c3 = cf[3]; c4 = cf[4]; c5 = cf[5]; clip = cf[6]; ptype = cf[7];
+                            if (A.noise != nullptr) nz = ld4(A.noise + ((size_t)step * A.B + b) * 256 + 4 * lane);
+                        }
                         const float4 lat = ld4(KEEP + 4 * lane);
                         const float xs[4] = {lat.x, lat.y, lat.z, lat.w}, es4[4] = {e.x, e.y, e.z, e.w}, ns[4] = {nz.x, nz.y, nz.z, nz.w};
                         float o[4];
+                        if constexpr (GRP) {
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            float x0, ep;
-                            if (ptype == 0.f) { ep = es4[i]; x0 = (xs[i] - c1 * ep) / c0; }
-                            else              { x0 = es4[i]; ep = (xs[i] - c0 * x0) / c1; }
-                            if (clip != 0.f) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-                            o[i] = c2 * x0 + c3 * ep + c5 * xs[i] + c4 * ns[i];
+                            for (int i = 0; i < 4; ++i) o[i] = cl_sched_elem(i == 3, xs[i], es4[i], ns[i], c0, c1, c2, c3, c4, c5, clip, ptype);
+                        } else {
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) {
+                                float x0, ep;
+                                if (ptype == 0.f) { ep = es4[i]; x0 = (xs[i] - c1 * ep) / c0; }
+                                else              { x0 = es4[i]; ep = (xs[i] - c0 * x0) / c1; }
+                                if (clip != 0.f) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+                                o[i] = c2 * x0 + c3 * ep + c5 * xs[i] + c4 * ns[i];
+                            }
                         }
                         const float4 nl = make_float4(o[0], o[1], o[2], o[3]);
                         st4(KEEP + 4 * lane, nl);
@@ -1118,7 +1231,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
             }
             cur ^= 1;
         }
-        row = row_next;
+        row = GRP ? row_nx : row_next;
     }
     DEN_DBG(3);
     if (epi && c == 0) st4(A.out + (size_t)b * 256 + 4 * lane, ld4(KEEP + 4 * lane));
@@ -1132,10 +1245,11 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
 }
 
 template <int C>
-static size_t cl_lds_bytes(int N, bool q) {
+static size_t cl_lds_bytes(int N, bool q, bool grp) {
     typedef ClG<C> G;
     const int stg = q ? 2 * (VP_LAYER + STG_TT + N * 1024) : ClRes<C>::FLOATS;    // (one condition token: resident block + changing rows)
-    return (size_t)(768 + 256 + stg + 512 + 512 + 2 * (G::NB > 128 ? G::NB : 128) + 1024 + 2 * G::S + 256 + 256 + 4) * sizeof(float);
+    const int sch = grp ? 12 + 256 : 0;                                            // (two wave groups: COEF | NZ, the same for every plan)
+    return (size_t)(768 + 256 + stg + 512 + 512 + 2 * (G::NB > 128 ? G::NB : 128) + 1024 + 2 * G::S + 256 + 256 + 4 + sch) * sizeof(float);
 }
 
 extern "C" size_t seeme_den_cluster_xchg_bytes(int B, int C) {       // (the several-token layout: the larger of the two)
@@ -1169,7 +1283,7 @@ static int launch_den_cluster(const ClArgs& ka0, hipStream_t st) {
     SEEME_HIP(hipGetDevice(&dev));
     SEEME_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     if (grid > cus || grid > 256) return seeme_fail("denoiser_sample_cluster: B x C exceeds one workgroup per CU of this device");
-    const size_t lds = cl_lds_bytes<C>(Q ? ka.s.N : 1, Q);
+    const size_t lds = cl_lds_bytes<C>(Q ? ka.s.N : 1, Q, ClGrp<WT, C, Q>::ON);
     if (lds > 160 * 1024 || lds <= 80 * 1024) return seeme_fail("denoiser_sample_cluster: LDS footprint must force one workgroup per CU");
     SEEME_HIP(hipFuncSetAttribute((const void*)k_den_cluster<WT, C, Q>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // granules and header are zeroed before EVERY launch (tags of an earlier launch must never match)
