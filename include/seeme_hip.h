@@ -801,6 +801,76 @@ int seeme_resnet_conv(const SeemeConv* c, int precision, const void* x, int B, i
 int seeme_resnet_stem_pack(const void* images, int image_format, int B, int H, int W, int precision, void* y, void* stream);
 int seeme_resnet_maxpool(int precision, const void* x, int B, int H, int W, int C, void* y, void* stream);
 
+/* ------------------------------------------------------------------ mesh and point-cloud rasteriser (csrc/render.hip)
+ * F frames of NF triangles over per-frame vertices, and P points shared by the frames, seen through a pinhole camera: per pixel the
+ * id of the nearest primitive and its inverse depth, then a flat-shaded RGB image.  Everything after the vertex stage is integer
+ * arithmetic, so the kernels, the plain-torch twin (seeme_amd/render.py render_torch) and tests/render_reference.py agree bit for
+ * bit on ids, inv_depth and dropped.
+ *
+ * Vertex stage, per frame f and vertex (x, y, z), fp32 inputs widened to double, every product, sum and quotient rounded on its own
+ * (no contraction).  M = cams[FC == 1 ? 0 : f], row-major world -> camera, rows 0..2 are read, left to right:
+ *     xc = ((M00 x + M01 y) + M02 z) + M03        yc, zc likewise from rows 1 and 2
+ *     X = rint(((fx xc) / zc + cx) 16)            Y = rint(((fy yc) / zc + cy) 16)          (rint: round half to even)
+ *     Qv = rint((znear / zc) 2^22)                the inverse depth: affine in screen space, so interpolating it is perspective-correct
+ * The vertex is valid iff zc is finite, zc >= znear, and X, Y are finite with |X|, |Y| <= SEEME_RENDER_COORD_MAX; then 0 <= Qv <=
+ * SEEME_RENDER_Q.  X, Y are in 1/SEEME_RENDER_SUB pixel; pixel (row i, col j) is sampled at (16 j, 16 i): pixel centres sit at
+ * integer coordinates (the OpenCV convention).
+ *
+ * Faces.  A face with an invalid corner is dropped whole and counted in dropped[f] (no near-plane clipping).  For the snapped
+ * corners A, B, C: area2 = (Bx-Ax)(Cy-Ay) - (By-Ay)(Cx-Ax); 0 draws nothing; negative: B and C (and their Q) are swapped, so both
+ * windings draw the same.  With e(U,V,P) = (Vx-Ux)(Py-Uy) - (Vy-Uy)(Px-Ux): w0 = e(B,C,P), w1 = e(C,A,P), w2 = e(A,B,P).  The pixel
+ * is covered iff for every k: w_k > 0, or w_k == 0 and the edge's (dx, dy) = V - U has dy > 0 or (dy == 0 and dx < 0) -- an edge
+ * shared by two triangles gives its pixels to exactly one of them.  The inverse depth at the pixel, in int64:
+ *     q = floor((w0 Q_A + w1 Q_B + w2 Q_C) / area2)
+ * Why 64 bits hold: |X|, |Y| <= 2^18 and a pixel's coordinates lie in 0..16 * 4095 < 2^16, so the difference of two corners is at
+ * most 2^19 in magnitude and that of a pixel and a corner below 2^19; a product of two such is at most 2^38, so |area2|, |w_k| <=
+ * 2^39.  q is evaluated on covered pixels only; there w_k >= 0 and w0 + w1 + w2 = area2, so 0 <= w_k <= area2, every product
+ * w_k Q_k <= 2^39 2^22 = 2^61, and the numerator, a convex combination of the Q times area2, as well: |products| <= 2^61 < 2^63,
+ * no partial sum exceeds the total, and 0 <= q <= 2^22.
+ *
+ * Points use the same vertex stage; the pixel is j = (X + 8) >> 4, i = (Y + 8) >> 4 (arithmetic shifts), a point_size square spans
+ * the offsets -((s-1)/2) .. s/2 on both axes, clipped to the image; q = Qv, id = NF + p.  An invalid point draws nothing and is not
+ * counted.
+ *
+ * Visibility.  key = (q << 32) | (0xFFFFFFFF - id), unsigned 64-bit; a pixel holds the MAXIMUM key over everything that covers it:
+ * nearer wins, then the lower id (a face beats a point at equal depth).  Key 0 is the empty pixel (id <= 2^31 - 2 keeps a real key
+ * above it).  A maximum does not depend on the order of arrival: the result is bitwise reproducible.
+ * Outputs: ids [F,H,W] int32 (-1 empty), inv_depth [F,H,W] int32 (0 empty; depth in metres = znear 2^22 / q), dropped [F] int32.
+ *
+ * Shading (a separate entry point) writes rgb [F,H,W,3] uint8 from ids: an empty pixel gets bg, a point pixel point_rgb[id - NF], a
+ * face pixel floor(base (0.3 + 0.7 |n_z| / |n|) + 0.5) per channel, n = (B-A) x (C-A) from the un-snapped camera-space corners
+ * (|n| = 0: the ratio counts as 0), base = palette[mesh_of_face[id]].  The twin evaluates this in float64, the kernel in fp32: a
+ * channel can differ by one where the value sits on a rounding boundary.
+ *
+ * 1 <= F <= 65535, FC = 1 or F, 1 <= H, W <= SEEME_RENDER_SIZE_MAX, 0 <= NV <= 2^24, NF, P >= 0 with NF + P <= 2^31 - 2 (NF > 0 needs
+ * NV > 0), 1 <= point_size <= SEEME_RENDER_POINT_MAX, fx, fy, cx, cy finite, znear finite and > 0.  The caller validates the face table
+ * (indices in 0..NV-1) and mesh_of_face (0..n_mesh-1) once: the entry points cannot look into device memory without a synchronisation.
+ * The kernels guard themselves as well: a face with an index outside 0..NV-1 draws nothing, is not counted and is never read; a
+ * mesh_of_face entry outside 0..n_mesh-1 shades as bg.  Plan: project every (frame, vertex) once into the workspace,
+ * one lane per (frame, face) walks the face's clamped bounding box and issues a 64-bit vector atomic max into the workspace's key
+ * image (a box above 256 pixels is walked by the whole wave), points likewise, and a resolve pass unpacks the keys.  No allocation,
+ * no synchronisation; workspace 16-byte aligned: keys [F,H,W] uint64, then the projected vertices [F,NV] int32 x 4. */
+#define SEEME_RENDER_SUB 16
+#define SEEME_RENDER_COORD_MAX 262144           /* 2^18 sub-pixel units */
+#define SEEME_RENDER_Q 4194304                  /* 2^22 */
+#define SEEME_RENDER_SIZE_MAX 4096
+#define SEEME_RENDER_POINT_MAX 8
+typedef struct {
+    const float* verts;             /* [F,NV,3] fp32, world frame */
+    const int32_t* faces;           /* [NF,3] vertex indices, shared by the frames */
+    const float* points;            /* [P,3] fp32, world frame, shared by the frames (NULL with P = 0) */
+    const float* cams;              /* [FC,4,4] fp32 row-major world -> camera */
+    int F, NV, NF, P, FC, H, W, point_size;
+    float fx, fy, cx, cy, znear;
+} SeemeRenderScene;
+size_t seeme_render_workspace_bytes(int F, int NV, int H, int W);     /* 0 for bad sizes */
+int seeme_render(const SeemeRenderScene* s, int32_t* ids, int32_t* inv_depth, int32_t* dropped, void* ws, size_t ws_bytes,
+                 void* stream);
+/* bg = r | g << 8 | b << 16; palette [n_mesh,3] and point_rgb [P,3] uint8 (point_rgb NULL with P = 0; mesh_of_face and palette NULL
+ * with NF = 0); ids as written by the render entry point for the same scene. */
+int seeme_render_shade(const SeemeRenderScene* s, const int32_t* ids, const int32_t* mesh_of_face, const uint8_t* palette,
+                       int n_mesh, const uint8_t* point_rgb, uint32_t bg, uint8_t* rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,12 @@ class Resnet50(C.Structure):
     _fields_ = [("precision", C.c_int), ("conv", Conv * RESNET50_NCONV), ("tap", fp * 5)]
 
 
+class RenderScene(C.Structure):
+    _fields_ = [("verts", fp), ("faces", fp), ("points", fp), ("cams", fp)] + \
+               [(n, C.c_int) for n in ("F", "NV", "NF", "P", "FC", "H", "W", "point_size")] + \
+               [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "znear")]
+
+
 GEO_AA_TO_QUAT, GEO_AA_TO_ROTMAT, GEO_QUAT_TO_ROTMAT, GEO_ROT6D_PROHMR, GEO_ROT6D_DIFFUSION = range(5)
 
 # name -> (restype, argtypes); every symbol of include/seeme_hip.h
@@ -235,6 +241,9 @@ _SIGNATURES = {
     "seeme_scene_views_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "seeme_scene_views": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, C.c_size_t, fp]),
     "seeme_crop_patches": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, fp, fp, C.c_int, C.c_int, fp, fp]),
+    "seeme_render_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "seeme_render": (C.c_int, [C.POINTER(RenderScene), fp, fp, fp, fp, C.c_size_t, fp]),
+    "seeme_render_shade": (C.c_int, [C.POINTER(RenderScene), fp, fp, fp, C.c_int, fp, C.c_uint32, fp, fp]),
     "seeme_pa_mpjpe_frames": (C.c_int, [fp, fp, fp, C.c_int, fp, fp]),
     "seeme_mesh_v2v_frames": (C.c_int, [fp, fp, fp, fp, fp, C.c_int, C.c_int, fp, fp]),
     "seeme_scene_min_dist2_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -539,3 +539,145 @@ def predict_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=N
              float(out["seam_cost"].mean()) if len(starts) > 1 else 0.0, args.output)
     return {"file": args.output, "n_frames": rec["n_frames"], "windows": len(starts), "path": out["path"].tolist(),
             "path_cost": float(out["path_cost"])}
+
+
+# ----------------------------------------------------------------------------- a predicted recording -> frames to look at
+RENDER_UP = {"egobody": (0.0, 1.0, 0.0), "gimo": (0.0, 1.0, 0.0)}     # the datasets' vertical axis
+RENDER_PALETTE = ((96, 152, 232), (236, 146, 84))                     # the wearer, the interactee
+RENDER_BG = (24, 24, 28)
+
+
+def _parse_size(text: str):
+    m = re.match(r"^(\d+)x(\d+)$", str(text))
+    if not m or not (1 <= int(m.group(1)) <= 4096 and 1 <= int(m.group(2)) <= 4096):
+        raise ValueError(f"--size is {text!r}: expected HxW with H and W in 1..4096, e.g. 480x640")
+    return int(m.group(1)), int(m.group(2))
+
+
+def render_main(argv: Optional[List[str]] = None, smpl_model=None) -> Dict:
+    """render.py: a recording .npz and the motion .npz that predict.py wrote for it -> uint8 frames [L,H,W,3] as a .npy (and PNGs):
+    the wearer's and the interactee's SMPL bodies, flat-shaded in two colours, and the scene cloud as points coloured by height, seen
+    from one fixed orbit camera or through the recording's own headset path.  No checkpoint is read."""
+    import numpy as np
+    from . import recording as R
+    from . import render as RD
+    from .smpl import SMPL
+    p = build_parser("render")
+    g = p.add_argument_group("rendering")
+    g.add_argument("--input", type=str, required=True, help="recording .npz (INTEGRATION.md K): the interactee, the scene, world2cam")
+    g.add_argument("--motion", type=str, required=True, help="the wearer's motion .npz, as predict.py writes it")
+    g.add_argument("--output", type=str, required=True, help="where the frames go: uint8 [L,H,W,3] as a .npy")
+    g.add_argument("--png_dir", type=str, default=None, help="also write one PNG per frame into this directory")
+    g.add_argument("--view", type=str, default="orbit", choices=["orbit", "ego"],
+                   help="orbit: one fixed camera for the whole recording; ego: the recording's world2cam [L,4,4]")
+    g.add_argument("--azimuth", type=float, default=30.0, help="orbit: degrees around --up")
+    g.add_argument("--elevation", type=float, default=20.0, help="orbit: degrees above the plane across --up")
+    g.add_argument("--fov", type=float, default=60.0, help="degrees spanned by the image width")
+    g.add_argument("--up", type=float, nargs=3, default=None, help="the world's vertical axis (default: the dataset's)")
+    g.add_argument("--camera", type=str, default=None, help="a .npy world2cam [4,4] or [L,4,4] in place of --view")
+    g.add_argument("--size", type=str, default="480x640", help="HxW")
+    g.add_argument("--point_size", type=int, default=2, help="side of a scene point's square in pixels, 1..8")
+    g.add_argument("--near", type=float, default=0.05, help="near plane in metres; a face with a corner nearer than it is dropped")
+    g.add_argument("--chunk_mb", type=float, default=256.0, help="bound on the device memory of one chunk of frames")
+    p.set_defaults(scene_points=20000)                                 # the scene cloud is thinned to at most this many points
+    args = p.parse_args(argv)
+    cfg = load_cfg(args, "test")
+    log = make_logger(cfg, "render", 0)
+    H, W = _parse_size(args.size)
+    if args.scene_points < 0:
+        raise ValueError(f"--scene_points is {args.scene_points}: expected >= 0 (0 draws no scene)")
+    if not 1 <= args.point_size <= RD.POINT_MAX:
+        raise ValueError(f"--point_size is {args.point_size}: expected 1..{RD.POINT_MAX}")
+    if not args.chunk_mb > 0:
+        raise ValueError(f"--chunk_mb is {args.chunk_mb}: expected a positive number of MiB")
+    name = str(cfg.DATASET_NAME)
+    up = tuple(args.up) if args.up is not None else RENDER_UP.get(name)
+    if up is None:
+        raise ValueError(f"DATASET_NAME is {name!r}: no default vertical axis is known for it, give --up x y z")
+    rec = R.load_recording(args.input)
+    n = int(rec["n_frames"])
+    mot = RD.load_motion(args.motion, n)
+    if args.camera is not None:
+        cam = np.asarray(np.load(args.camera, allow_pickle=False), np.float64)
+        if cam.shape == (4, 4):
+            cam = cam[None]
+        if cam.shape not in ((1, 4, 4), (n, 4, 4)):
+            raise ValueError(f"--camera {args.camera}: world2cam is {cam.shape}: expected [4,4] or [{n},4,4] (L = {n})")
+        R.check_world2cam(cam, cam.shape[0], f"--camera {args.camera}")
+    elif args.view == "ego":
+        if "world2cam" not in rec:
+            raise ValueError(f"{args.input}: --view ego needs the recording's world2cam [L,4,4] (the headset path), and the file holds none; "
+                             "use --view orbit or --camera")
+        cam = rec["world2cam"]
+    else:
+        cam = None                                                      # fitted below, once the bodies are known
+    if smpl_model is None:
+        path = str(cfg.model.smpl_path)
+        smpl_model = SMPL(model_path=path, gender="neutral") if os.path.exists(path) else SMPL.synthetic(int(cfg.SEED_VALUE))
+    faces1 = smpl_model.faces_tensor.detach().cpu().long()
+    V = int(smpl_model.v_template.shape[0])
+    solid = (faces1[:, 0] != faces1[:, 1]) & (faces1[:, 1] != faces1[:, 2]) & (faces1[:, 0] != faces1[:, 2])
+    if faces1.numel() == 0 or not bool(solid.any()) or int(faces1.min()) < 0 or int(faces1.max()) >= V:
+        raise ValueError("the SMPL model's face table holds no non-degenerate face inside its vertices (the synthetic stand-in has "
+                         "none): set model.smpl_path to a real SMPL model file to render bodies")
+    if not torch.cuda.is_available():
+        raise SystemExit("rendering runs on the HIP path: an MI355X is required (no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    smpl_model = smpl_model.to(dev)
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
+
+    def pose69(bp):                                                     # GIMO's 21 body joints, padded as mld.py:807-813 does
+        return np.concatenate([bp, np.zeros((bp.shape[0], 69 - bp.shape[1]), np.float32)], axis=1) if bp.shape[1] < 69 else bp
+
+    people = []                                                         # the wearer first: palette row 0
+    for src, betas in ((mot, rec.get("wearer_betas", np.zeros(10, np.float32))), (rec, rec["betas"])):
+        people.append({"global_orient": to(src["global_orient"]), "body_pose": to(pose69(src["body_pose"])), "transl": to(src["transl"]),
+                       "betas": to(betas)[None]})
+
+    def bodies(lo, hi, verts=True):
+        out = [smpl_model(betas=q["betas"], body_pose=q["body_pose"][lo:hi], global_orient=q["global_orient"][lo:hi],
+                          transl=q["transl"][lo:hi], return_verts=verts) for q in people]
+        return torch.cat([o.vertices if verts else o.joints[:, :24] for o in out], dim=1)
+
+    faces = torch.cat([faces1, faces1 + V]).to(torch.int32).to(dev)
+    mesh_of_face = torch.cat([torch.zeros(faces1.shape[0]), torch.ones(faces1.shape[0])]).to(torch.int32).to(dev)
+    palette = torch.tensor(RENDER_PALETTE, dtype=torch.uint8, device=dev)
+    cloud = rec.get("scene", rec.get("scene_vertices"))
+    points = point_rgb = None
+    if cloud is not None and args.scene_points > 0:
+        cloud = cloud[np.isfinite(cloud).all(axis=1)]
+        cloud = cloud[::max(1, -(-cloud.shape[0] // args.scene_points))]   # every k-th point, down to at most --scene_points
+        if cloud.shape[0]:
+            points, point_rgb = to(cloud), torch.from_numpy(RD.height_colours(cloud, up)).to(dev)
+    with torch.no_grad():
+        if cam is None:
+            cam = RD.orbit_camera(bodies(0, n, verts=False).cpu().numpy(), args.azimuth, args.elevation, args.fov, up, aspect=W / H,
+                                  margin=1.25)[None]                    # the joints of both bodies, with room for the flesh around them
+        cams = to(cam)
+        K = RD.intrinsics(args.fov, (H, W))
+        d = os.path.dirname(os.path.abspath(args.output))
+        os.makedirs(d, exist_ok=True)
+        if args.png_dir:
+            os.makedirs(args.png_dir, exist_ok=True)
+        frames = np.lib.format.open_memmap(args.output, "w+", np.uint8, (n, H, W, 3))
+        per_frame = H * W * (8 + 4 + 4 + 3) + 2 * V * (12 + 16)          # keys, ids, inverse depth, rgb; vertices and their projections
+        step = max(1, min(n, int(args.chunk_mb * (1 << 20)) // per_frame))
+        dropped = 0
+        for lo in range(0, n, step):
+            hi = min(n, lo + step)
+            verts = bodies(lo, hi)
+            c = cams[lo:hi] if cams.shape[0] > 1 else cams
+            r = RD.render_hip(verts, faces, c, K, (H, W), points=points, near=args.near, point_size=args.point_size,
+                              chunk_mb=args.chunk_mb)
+            rgb = RD.shade_hip(verts, faces, c, r["ids"], mesh_of_face, palette, points, point_rgb, RENDER_BG).cpu().numpy()
+            dropped += int(r["dropped"].sum())
+            frames[lo:hi] = rgb
+            if args.png_dir:
+                for f in range(lo, hi):
+                    RD.write_png(os.path.join(args.png_dir, f"frame_{f:06d}.png"), rgb[f - lo])
+        frames.flush()
+        del frames
+    log.info("%d frames of %d x %d (%s), %d scene points; %d faces dropped for a corner outside the view volume (near %.3f m); written to %s",
+             n, H, W, "camera file" if args.camera else args.view, 0 if points is None else int(points.shape[0]), dropped, args.near,
+             args.output)
+    return {"file": args.output, "n_frames": n, "size": (H, W), "dropped": dropped, "scene_points": 0 if points is None else int(points.shape[0])}
