@@ -871,6 +871,62 @@ int seeme_render(const SeemeRenderScene* s, int32_t* ids, int32_t* inv_depth, in
 int seeme_render_shade(const SeemeRenderScene* s, const int32_t* ids, const int32_t* mesh_of_face, const uint8_t* palette,
                        int n_mesh, const uint8_t* point_rgb, uint32_t bg, uint8_t* rgb, void* stream);
 
+/* ------------------------------------------------------------------ ProHMR-scene pose head (csrc/flow_head.hip)
+ * The sampling direction of SMPLFlow (EgoHMR/models/prohmr/smpl_flow.py): nflows ConditionalGlow(144, 1024, 4, 2, context 2566) =
+ * four layers of ActNorm -> LULinear -> AdditiveCoupling, inverted (layers 3 down to 0; inside a layer coupling^-1, LU^-1,
+ * ActNorm^-1), plus FCHead for betas and the weak-perspective camera, eval mode, fp32 throughout.
+ *
+ * Inputs: ctx [L,2566] = [cam_cx/f, cam_cy/f, box_cx/f, box_cy/f, box_size/f, f/1500, image 2048, scene 512] per frame, z [L,S,144]
+ * the base-distribution draws (z = 0 is the mode).  Row (l, s) uses ctx[l].  With x = z[l, s], per layer k = 3..0 whose identity
+ * features are the indices 2j + p_k (p_k = bit k of id_parity; j = 0..71) and whose transform features are the others:
+ *     h  = id_w[k] x[identity] + (ctx_w[k] ctx[l] + ctx_b[k])                               initial_layer, split by columns
+ *     for the two blocks b:  h += lin_w[k][2b+1] relu(bn(lin_w[k][2b] relu(bn(h)))) + res_b[k][b]
+ *                            bn(v) = v * bn_s + bn_o, the eval-mode BatchNorm; the first Linear's bias is folded into the second
+ *                            BatchNorm's offset
+ *     x[transform] -= fin_w[k] h + fin_b[k]                                                 additive coupling, inverted
+ *     x = (lu_w[k] x) * act_s[k] + act_o[k]                                                 lu_w = inv(L U), a dense 144 x 144 matrix;
+ *                                                                                           act_s = exp(-log_scale),
+ *                                                                                           act_o = -(lu_w bias + shift) act_s
+ * Outputs: pose6d [L,S,144] = x; rotmat [L,S,24,3,3]: per joint a1 = x[6j..6j+2], a2 = x[6j+3..6j+5], b1 = a1 / max(|a1|, 1e-12),
+ * b2 likewise from a2 - (b1.a2) b1, columns (b1, b2, b1 x b2) (rot6d_to_rotmat, 'prohmr' order); log_prob [L,S] =
+ * -|z|^2 / 2 + log_const, log_const = sum over layers of (sum log_scale + sum log diag U) - 72 log 2 pi (the coupling is additive, so
+ * log|det| depends on neither z nor ctx); betas [L,10], cam [L,3] = fc_w relu(ctx_w[4] ctx[l] + ctx_b[4]) + fc_b with init_betas /
+ * init_cam folded into fc_b.
+ *
+ * Every matrix is row-major [out, in] fp32, 16-byte aligned.  ctx_w stacks the context columns of the four initial layers and
+ * fc_head.layers.0: [5 * 1024, SEEME_FLOW_CTX_PAD], columns 2566.. zero; id_w [4][1024][80], columns 72.. zero.
+ * 1 <= S <= SEEME_FLOW_S_MAX, L >= 1, L * S <= SEEME_FLOW_ROWS_MAX.  A row's result does not depend on the rows it shares a
+ * workgroup with.  Three launches on `stream`, no allocation, no synchronisation; workspace 16-byte aligned, [L, 5120] fp32. */
+#define SEEME_FLOW_DIM 144
+#define SEEME_FLOW_HIDDEN 1024
+#define SEEME_FLOW_LAYERS 4
+#define SEEME_FLOW_CTX 2566
+#define SEEME_FLOW_CTX_PAD 2576
+#define SEEME_FLOW_CTX_COLS 5120
+#define SEEME_FLOW_S_MAX 32
+#define SEEME_FLOW_ROWS_MAX 1048576
+typedef struct {
+    const float* ctx_w;             /* [5120, 2576] */
+    const float* ctx_b;             /* [5120] */
+    const float* id_w;              /* [4][1024][80] */
+    const float* lin_w;             /* [4][4][1024][1024]: block 0 Linear 0, 1, block 1 Linear 0, 1 */
+    const float* bn_s;              /* [4][4][1024] the BatchNorm in front of each of them, as scale ... */
+    const float* bn_o;              /* [4][4][1024] ... and offset */
+    const float* res_b;             /* [4][2][1024] bias of each block's second Linear */
+    const float* fin_w;             /* [4][72][1024] */
+    const float* fin_b;             /* [4][72] */
+    const float* lu_w;              /* [4][144][144] */
+    const float* act_s;             /* [4][144] */
+    const float* act_o;             /* [4][144] */
+    const float* fc_w;              /* [13][1024] */
+    const float* fc_b;              /* [13] */
+    int id_parity;                  /* bit k: layer k's identity features are the odd indices */
+    float log_const;
+} SeemeFlowHead;
+size_t seeme_flow_head_workspace_bytes(int L, int S);                  /* 0 for bad sizes */
+int seeme_flow_head(const SeemeFlowHead* w, const float* ctx, const float* z, int L, int S, float* pose6d, float* rotmat, float* betas,
+                    float* cam, float* log_prob, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,6 +165,11 @@ class RenderScene(C.Structure):
                [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "znear")]
 
 
+class FlowHead(C.Structure):
+    _fields_ = [(n, fp) for n in ("ctx_w", "ctx_b", "id_w", "lin_w", "bn_s", "bn_o", "res_b", "fin_w", "fin_b", "lu_w", "act_s",
+                                  "act_o", "fc_w", "fc_b")] + [("id_parity", C.c_int), ("log_const", C.c_float)]
+
+
 GEO_AA_TO_QUAT, GEO_AA_TO_ROTMAT, GEO_QUAT_TO_ROTMAT, GEO_ROT6D_PROHMR, GEO_ROT6D_DIFFUSION = range(5)
 
 # name -> (restype, argtypes); every symbol of include/seeme_hip.h
@@ -251,6 +256,8 @@ _SIGNATURES = {
     "seeme_scene_inside_count_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "seeme_scene_inside_count": (C.c_int, [fp, fp, C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, C.c_size_t, fp]),
     "seeme_mesh_winding": (C.c_int, [fp, fp, C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp]),
+    "seeme_flow_head_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "seeme_flow_head": (C.c_int, [C.POINTER(FlowHead), fp, fp, C.c_int, C.c_int, fp, fp, fp, fp, fp, fp, C.c_size_t, fp]),
     "seeme_resnet50_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "seeme_resnet50_encode": (C.c_int, [C.POINTER(Resnet50), fp, C.c_int, C.c_int, fp, fp, C.c_size_t, fp]),
     "seeme_resnet_conv": (C.c_int, [C.POINTER(Conv), C.c_int, fp, C.c_int, C.c_int, C.c_int, fp, C.c_int, fp, fp]),

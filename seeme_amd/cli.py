@@ -541,6 +541,120 @@ def predict_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=N
             "path_cost": float(out["path_cost"])}
 
 
+# ----------------------------------------------------------------------------- a recording without the interactee -> one with
+def load_proscene(model, state: Dict, path: str) -> str:
+    """The ProHMR-scene modules of `model` (scene_enc, backbone, flow, as far as it has them) from a SEE-ME state dict (prefix
+    ``proscene.``) or from a ProHMR-scene one (no prefix; its smpl*, discriminator.* and loss entries are not read, mld.py:197-203),
+    each strictly.  A file without the flow entries is a KeyError naming the first missing key."""
+    from .prohmr_head import flow_state_from_checkpoint
+    prefix = "proscene." if any(k.startswith("proscene.") for k in state) else ""
+    kind = "SEE-ME" if prefix else "ProHMR-scene"
+    model.proscene.flow.load_state_dict(flow_state_from_checkpoint(state), strict=True)
+    for name in ("scene_enc", "backbone"):
+        if hasattr(model.proscene, name):
+            sub = {k[len(prefix + name) + 1:]: v for k, v in state.items() if k.startswith(prefix + name + ".")}
+            if not sub:
+                raise KeyError(f"{path}: a {kind} checkpoint without '{prefix}{name}.*': the model's {name} cannot be loaded from it")
+            getattr(model.proscene, name).load_state_dict(sub, strict=True)
+    return kind
+
+
+def estimate_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=None) -> Dict:
+    """estimate.py: a recording .npz WITHOUT the interactee (video or image_crops, center, scale, cam_intrinsics, world2cam,
+    scene_vertices) -> the same recording with the interactee's global_orient, body_pose, transl and betas as the
+    ProHMR-scene head estimates them, in the recording's world frame: a file predict.py accepts."""
+    import numpy as np
+    from . import crops as CR
+    from . import geometry as G
+    from . import prohmr_head as PH
+    from . import recording as R
+    p = build_parser("estimate")
+    g = p.add_argument_group("recording")
+    g.add_argument("--input", type=str, required=True, help="recording .npz without interactee keys (INTEGRATION.md N)")
+    g.add_argument("--output", type=str, required=True, help="where the recording with the interactee goes (.npz)")
+    g.add_argument("--video", type=str, default=None, help="decoded frames, uint8 RGB [L,H,W,3] as a .npy (opened memory-mapped), in "
+                   "place of the recording's video key")
+    g.add_argument("--num_samples", type=int, default=1, help="samples per frame, 1..32: sample 0 is the mode (z = 0)")
+    g.add_argument("--seed", type=int, default=None, help="seed of the draws (default: SEED_VALUE)")
+    g.add_argument("--save_samples", action="store_true", help="also store interactee_samples_{global_orient,body_pose,transl} [L,S,...]")
+    g.add_argument("--chunk_frames", type=int, default=64, help="frames per pass: bounds the scene clouds (scene_points x 12 bytes each)")
+    p.set_defaults(scene_points=None, frames=16)
+    args = p.parse_args(argv)
+    cfg = load_cfg(args, "test")
+    cfg.model.interactee_head = True
+    if args.scene_points is not None:
+        cfg.TEST.SCENE_VIEW_POINTS = args.scene_points
+    args.scene_points = P = int(cfg.TEST.get("SCENE_VIEW_POINTS", 20000))
+    S = args.num_samples
+    if not 1 <= S <= PH.S_MAX:
+        raise ValueError(f"--num_samples is {S}: expected 1..{PH.S_MAX}")
+    if args.chunk_frames < 1:
+        raise ValueError(f"--chunk_frames is {args.chunk_frames}: expected >= 1")
+    log = make_logger(cfg, "estimate", 0)
+    if not torch.cuda.is_available():
+        raise SystemExit("the estimate runs on the HIP path: an MI355X is required (no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    model, _dm = build(cfg, dev, args, datamodule, smpl_model)
+    if "scene" not in cfg.model.condition or not model.image_backbone:
+        raise ValueError("estimate needs the scene encoder and the image backbone: model.condition with 'scene' and 'image', and "
+                         "model.image_backbone: true")
+    ckpt = args.checkpoint or cfg.TEST.get("CHECKPOINTS")
+    if not ckpt:
+        raise ValueError("TEST.CHECKPOINTS (or --checkpoint) is required")
+    ck = read_checkpoint(ckpt)
+    log.info("Loading the %s modules of %s", load_proscene(model, ck.get("state_dict", ck), ckpt), ckpt)
+    model = model.to(dev).eval()
+    rec = R.load_recording(args.input, video=args.video, require_interactee=False)
+    n = int(rec["n_frames"])
+    view = R.opencv_views(rec["world2cam"], model.interactee_camera_axes)               # [L,4,4] float64: world -> OpenCV camera
+    verts = torch.from_numpy(np.ascontiguousarray(rec["scene_vertices"], np.float32)).to(dev)
+    gen = torch.Generator().manual_seed(int(cfg.SEED_VALUE) if args.seed is None else args.seed)
+    z = PH.draw_z(n, S, gen)                                            # drawn for the whole recording: chunking changes nothing
+    got = {k: [] for k in ("rotmat", "betas", "cam", "log_prob", "transl", "count")}
+    with torch.no_grad():
+        for lo in range(0, n, args.chunk_frames):
+            hi = min(n, lo + args.chunk_frames)
+            c, s_ = rec["center"][lo:hi], rec["scale"][lo:hi]
+            if "video" in rec:
+                frames = torch.from_numpy(np.ascontiguousarray(rec["video"][lo:hi])).to(dev)
+                patches = CR.crop_patches_hip(frames, np.arange(hi - lo), PH.head_box(c, s_))
+            else:
+                patches = torch.from_numpy(np.ascontiguousarray(rec["image_crops"][lo:hi])).to(dev)
+            sv = R.scene_views_hip(verts, torch.from_numpy(view[lo:hi]).float().to(dev), P)
+            count = sv["count"].cpu()
+            if bool((count == 0).any()):
+                f = lo + int(torch.nonzero(count == 0)[0])
+                raise ValueError(f"{args.input}: frame {f} sees no scene vertex (scene_view_count 0): its camera pose looks away from "
+                                 "scene_vertices (is TEST.INTERACTEE_CAMERA_AXES right for this world2cam?)")
+            out = model.estimate_interactee(patches, sv["cloud"], c, s_, rec["cam_intrinsics"][lo:hi], z=z[lo:hi])
+            for k in ("rotmat", "betas", "cam", "log_prob", "transl"):
+                got[k].append(out[k])
+            got["count"].append(count)
+    cat = {k: torch.cat(v) for k, v in got.items()}
+    aa = G.rotmat_to_aa_torch(cat["rotmat"].double()).reshape(n, S, 72)                 # camera frame, every sample
+    betas = cat["betas"].double().mean(dim=0)
+    # to the world; SMPL turns about the rest pelvis of the betas the body is posed with: the file's betas, the mean
+    J0 = R.rest_pelvis(model.smpl_model, betas[None].to(dev))[0].double()
+    go, tr = R.camera_body_to_world(aa[:, :, :3], cat["transl"].double()[:, None].expand(n, S, 3), J0, rec["world2cam"],
+                                    model.interactee_camera_axes)
+    f32 = lambda t: t.float().cpu().numpy()
+    with np.load(args.input, allow_pickle=False) as zf:
+        res = {k: zf[k] for k in zf.files}
+    res.update(global_orient=f32(go[:, 0]), body_pose=f32(aa[:, 0, 3:]), transl=f32(tr[:, 0]), betas=f32(betas),
+               interactee_betas_frames=f32(cat["betas"]), interactee_cam=f32(cat["cam"]), interactee_log_prob=f32(cat["log_prob"]),
+               scene_view_count=cat["count"].numpy())
+    if args.save_samples:
+        res.update(interactee_samples_global_orient=f32(go), interactee_samples_body_pose=f32(aa[:, :, 3:]),
+                   interactee_samples_transl=f32(tr))
+    d = os.path.dirname(os.path.abspath(args.output))
+    os.makedirs(d, exist_ok=True)
+    with open(args.output, "wb") as f:
+        np.savez(f, **res)
+    log.info("%d frames, %d samples each; mean log-probability of the mode %.2f; written to %s", n, S,
+             float(cat["log_prob"][:, 0].mean()), args.output)
+    return {"file": args.output, "n_frames": n, "num_samples": S}
+
+
 # ----------------------------------------------------------------------------- a predicted recording -> frames to look at
 RENDER_UP = {"egobody": (0.0, 1.0, 0.0), "gimo": (0.0, 1.0, 0.0)}     # the datasets' vertical axis (INTEGRATION.md M)
 RENDER_PALETTE = ((96, 152, 232), (236, 146, 84))                     # the wearer, the interactee

@@ -328,12 +328,15 @@ class _SceneEncoderHolder(nn.Module):
     """``proscene`` -- the sub-modules of ProHMRScene on the path: ``scene_enc`` (prohmr_scene.py:102-104) for a scene condition and,
     with ``model.image_backbone``, the ResNet-50 ``backbone`` (prohmr_scene.py:33-34, 99-100) for an image condition."""
 
-    def __init__(self, scene: bool = True, backbone: bool = False):
+    def __init__(self, scene: bool = True, backbone: bool = False, flow: bool = False):
         super().__init__()
         if scene:
             self.scene_enc = ResnetPointnet(512, 256)
         if backbone:
             self.backbone = ResNet50()
+        if flow:                                    # model.interactee_head: the pose head SMPLFlow (prohmr_scene.py:36-39)
+            from .prohmr_head import SMPLFlowHead
+            self.flow = SMPLFlowHead()
 
     def encode_scene(self, scene):
         return self.scene_enc(scene)
@@ -455,8 +458,16 @@ class MLD(nn.Module):
         self.image_backbone = bool(cfg.model.get("image_backbone", False)) and "image" in self.condition
         if "image" in self.condition:                                     # mld.py:251-255; trainable in stage 2
             self.output_images = nn.Sequential(nn.ReLU(), nn.Linear(IMAGE_FEAT_DIM, 256))
-        if "scene" in self.condition or self.image_backbone:              # mld.py:182-207, 257-261
-            self.proscene = _SceneEncoderHolder(scene="scene" in self.condition, backbone=self.image_backbone)
+        # model.interactee_head: ProHMR-scene's pose head (proscene.flow, seeme_amd/prohmr_head.py) for estimate_interactee; frozen,
+        # always eval.  Off: no such entries in the state dict
+        self.interactee_head = cfg.model.get("interactee_head", False)
+        if not isinstance(self.interactee_head, bool):
+            raise ValueError(f"model.interactee_head must be true or false, got {self.interactee_head!r}")
+        # diag(axes) takes the recording's camera frame to the image's OpenCV frame, in which the head works (recording.opencv_views)
+        from .recording import check_camera_axes
+        self.interactee_camera_axes = check_camera_axes(cfg.TEST.get("INTERACTEE_CAMERA_AXES", [1, -1, -1]))
+        if "scene" in self.condition or self.image_backbone or self.interactee_head:     # mld.py:182-207, 257-261
+            self.proscene = _SceneEncoderHolder(scene="scene" in self.condition, backbone=self.image_backbone, flow=self.interactee_head)
             for p in self.proscene.parameters():
                 p.requires_grad = False
         if self.image_backbone:
@@ -1245,6 +1256,45 @@ class MLD(nn.Module):
         joints_all = joints_all.view(B, K, min_len, 24, 3)
         return {"m_rst_all": f_rst.view(B, K, min_len, -1), "joints_rst_all": joints_all, "lat_t_all": z, "lengths": lengths,
                 "hyp_metrics": hyp_pairdist_hip(joints_all, lengths)}
+
+    @torch.no_grad()
+    def estimate_interactee(self, crops_or_feats, scene_views_or_feats, center, scale, intrinsics, z=None, num_samples: int = 1,
+                            generator=None):
+        """The interactee from what a headset records, in the image's OpenCV camera frame (``ProHMRScene.forward_step`` without its
+        losses, prohmr_scene.py:108-233).  crops_or_feats: uint8 [L,224,224,3] / float32 [L,3,224,224] crops cut by
+        ``prohmr_head.head_box`` (needs model.image_backbone) or pooled features [L,2048]; scene_views_or_feats: clouds [L,P,3] in
+        the camera frame (needs a 'scene' condition) or features [L,512]; center [L,2], scale [L]; intrinsics (f, cx, cy) in pixels,
+        [3] or [L,3].  z [L,S,144] or, without it, sample 0 = the mode and num_samples - 1 draws of `generator`.
+        -> dict: pose6d [L,S,144], rotmat [L,S,24,3,3], betas [L,10], cam [L,3], log_prob [L,S], transl [L,3], ctx [L,2566]."""
+        from . import prohmr_head as PH
+        if not self.interactee_head:
+            raise NotImplementedError("estimate_interactee needs the pose head: set model.interactee_head: true (INTEGRATION.md N)")
+        dev = self.proscene.flow.fc_head.init_cam.device
+        x = crops_or_feats.to(dev)
+        if x.dim() == 4:
+            if not self.image_backbone:
+                raise NotImplementedError("estimate_interactee was given crops, and the ResNet-50 backbone is off: set "
+                                          "model.image_backbone: true or pass its pooled features [L,2048]")
+            x = self.proscene.encode_image(x)
+        sc = scene_views_or_feats.to(dev)
+        if sc.dim() == 3:
+            if "scene" not in self.condition:
+                raise NotImplementedError("estimate_interactee was given scene clouds, and the model has no scene encoder ('scene' is "
+                                          "not in model.condition): pass its features [L,512]")
+            sc = self.proscene.encode_scene(sc.float().contiguous())
+        n = x.shape[0]
+        intr = torch.as_tensor(intrinsics, dtype=torch.float32, device=dev)
+        intr = intr.expand(n, 3) if intr.dim() == 1 else intr
+        if tuple(intr.shape) != (n, 3):
+            raise ValueError(f"intrinsics are {tuple(intr.shape)}: expected [3] or [{n},3] = (f, cx, cy)")
+        center = torch.as_tensor(center, dtype=torch.float32, device=dev)
+        scale = torch.as_tensor(scale, dtype=torch.float32, device=dev)
+        ctx = PH.context_rows(x.float(), sc.float(), center, scale, intr[:, 0], intr[:, 1], intr[:, 2])
+        if z is None:
+            z = PH.draw_z(n, int(num_samples), generator, dev)
+        pose6d, rotmat, betas, cam, log_prob = PH.flow_head_hip(self.proscene.flow, ctx, z.to(dev, torch.float32))
+        transl = PH.cam_to_transl(cam, center, scale, intr[:, 0], intr[:, 1], intr[:, 2])
+        return {"pose6d": pose6d, "rotmat": rotmat, "betas": betas, "cam": cam, "log_prob": log_prob, "transl": transl, "ctx": ctx}
 
     @torch.no_grad()
     def predict_recording(self, batch_of_windows, n_frames, overlap=None, betas=None, medoid_weight=None, num_hypotheses=None,

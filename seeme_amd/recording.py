@@ -463,7 +463,75 @@ def choose_frames(video_index, starts, lengths) -> List[int]:
     return rows
 
 
-def load_recording(path: str, video: Optional[str] = None) -> Dict[str, np.ndarray]:
+def check_intrinsics(K, n_frames: int, what: str = "cam_intrinsics") -> np.ndarray:
+    """cam_intrinsics, [3] or [L,3] = (f, cx, cy) in pixels -> float32 [L,3]; every value finite and f > 0, or a ValueError that names
+    the first frame where not."""
+    K = np.asarray(K)
+    if K.dtype.kind not in "fiu" or K.shape not in ((3,), (n_frames, 3)):
+        raise ValueError(f"{what}: cam_intrinsics is {K.shape} {K.dtype}: expected numbers [3] or [{n_frames},3] = (f, cx, cy) in pixels")
+    K = np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 3), (n_frames, 3))
+    with np.errstate(invalid="ignore"):
+        bad = ~np.isfinite(K).all(axis=1) | ~(K[:, 0] > 0)
+    if bad.any():
+        f = int(np.argmax(bad))
+        raise ValueError(f"{what}: cam_intrinsics of frame {f} is {K[f].tolist()}: (f, cx, cy) must be finite with f > 0")
+    return np.ascontiguousarray(K, np.float32)
+
+
+def check_camera_axes(axes, what: str = "TEST.INTERACTEE_CAMERA_AXES") -> Tuple[int, int, int]:
+    """Three entries of +-1 with product +1: D = diag(axes) takes the recording's camera frame to the image's OpenCV frame (x right,
+    y down, z forward).  [1,-1,-1] is EgoBody's (ADD_TRANS of seeme_amd/data.py), [1,1,1] says world2cam is OpenCV already."""
+    try:
+        a = [v for v in axes]
+    except TypeError:
+        a = None
+    if a is None or len(a) != 3 or any(isinstance(v, bool) or v not in (1, -1) for v in a) or a[0] * a[1] * a[2] != 1:
+        raise ValueError(f"{what} must be three entries of +1 or -1 with product +1 (a rotation), got {axes!r}")
+    return tuple(int(v) for v in a)
+
+
+def opencv_views(world2cam, axes) -> np.ndarray:
+    """[L,4,4] float64: D world2cam[l] with D = diag(axes, 1), the map from the recording's world frame to frame l's OpenCV camera frame."""
+    D = np.diag(np.array(list(check_camera_axes(axes)) + [1], np.float64))
+    return D[None] @ np.asarray(world2cam, np.float64)
+
+
+def camera_body_to_world(global_orient, cam_t, J0, world2cam, axes):
+    """A body estimated in the image's OpenCV camera frame -> the recording's world frame, by the rigid parts of
+    inv(D world2cam[l]).  global_orient, cam_t [L,3] or [L,S,3] (axis-angle; ProHMR adds cam_t to the body posed WITHOUT a
+    translation, prohmr_scene.py:177-212, and SMPL turns about its rest pelvis, so cam_t is SMPL's transl in that frame); J0 [3] the
+    rest pelvis of the betas the body is posed with; world2cam [L,4,4].  -> (global_orient, transl) of the same shapes."""
+    inv = rigid_inverse(torch.from_numpy(opencv_views(world2cam, axes)))
+    A, a = (t.to(global_orient.device) for t in rigid_parts(inv))
+    for _ in range(global_orient.dim() - 2):
+        A, a = A[:, None], a[:, None]
+    return reframe_smpl(global_orient, cam_t, J0, A, a)
+
+
+_ESTIMATE_KEYS = ("center", "scale", "cam_intrinsics", "world2cam", "scene_vertices")
+
+
+def _check_estimate_input(rec, n: int, path: str) -> None:
+    """What ``estimate`` reads of a recording without interactee keys: the box, the intrinsics, the camera path, the scene's vertices
+    and an image for EVERY recording frame."""
+    missing = [k for k in _ESTIMATE_KEYS if k not in rec]
+    if missing:
+        raise ValueError(f"{path}: missing {missing}; estimating the interactee needs {list(_ESTIMATE_KEYS)} and video or image_crops")
+    src = "video" if "video" in rec else "image_crops" if "image_crops" in rec else None
+    if src is None:
+        raise ValueError(f"{path}: holds neither video nor image_crops: the interactee is estimated from the frames' images")
+    for k, shape in (("center", (n, 2)), ("scale", (n,))):
+        if rec[k].dtype.kind != "f" or rec[k].shape != shape:
+            raise ValueError(f"{path}: {k} is {rec[k].shape} {rec[k].dtype}: expected floats {list(shape)} (L = {n})")
+        rec[k] = np.asarray(rec[k], np.float32)
+    vi = rec["video_index"]
+    if vi.shape[0] != n:                                   # strictly increasing inside 0..L-1: fewer than L entries skip a frame
+        f = int(np.argmax(vi != np.arange(vi.shape[0]))) if (vi != np.arange(vi.shape[0])).any() else int(vi.shape[0])
+        raise ValueError(f"{path}: frame {f} has no stored image (video_index skips it): every recording frame needs one; filling "
+                         "between sparse estimates is not built")
+
+
+def load_recording(path: str, video: Optional[str] = None, require_interactee: bool = True) -> Dict[str, np.ndarray]:
     """A recording ``.npz`` (read with allow_pickle=False: an object array is refused): the INTERACTEE's global_orient [L,3],
     body_pose [L,69|63], transl [L,3], betas [10]; optionally scene [P,3], image_feats [L,2048], wearer_betas [10].  float32.
     A moving camera adds world2cam [L,4,4], the rigid map from the recording's world frame to every frame's camera frame (float64:
@@ -474,11 +542,22 @@ def load_recording(path: str, video: Optional[str] = None) -> Dict[str, np.ndarr
     [L], the interactee's box per recording frame, ``crops.patch_box``), or image_crops [Lf,224,224,3] uint8 (patches already cut).
     video_index [Lf] integers names the recording frame of every stored frame, strictly increasing in 0..L-1; without it Lf = L and
     it is the identity.  video and image_crops stay uint8.  `video`: a ``.npy`` of the frames, opened memory-mapped, in place of the
-    video key."""
+    video key.
+
+    cam_intrinsics, [3] or [L,3] = (f, cx, cy) in pixels, is validated when present (``check_intrinsics``) and returned as [L,3].
+    require_interactee=False reads the INPUT of ``estimate``: a recording WITHOUT the four interactee keys, whose
+    length L is that of center [L,2]; it needs center, scale, cam_intrinsics, world2cam, scene_vertices and an image per frame.  A
+    file that holds interactee keys is refused there: it is an input of predict already."""
     with np.load(path, allow_pickle=False) as z:
         missing = [k for k in _REC_KEYS if k not in z.files]
-        if missing:
+        if require_interactee and missing:
             raise ValueError(f"{path}: missing {missing}; a recording holds {list(_REC_KEYS)} of the interactee")
+        if not require_interactee and len(missing) < len(_REC_KEYS):
+            raise ValueError(f"{path}: holds {[k for k in _REC_KEYS if k in z.files]} of the interactee already; require_interactee=False "
+                             "reads a recording WITHOUT them (the input of estimate), this one is an input of predict")
+        if not require_interactee and "center" not in z.files:
+            raise ValueError(f"{path}: missing ['center']; a recording without interactee keys takes its length from center [L,2]")
+        intrinsics = z["cam_intrinsics"] if "cam_intrinsics" in z.files else None
         rec = {k: np.asarray(z[k], np.float32) for k in _REC_KEYS + ("scene", "image_feats", "wearer_betas", "scene_vertices")
                if k in z.files}
         if "world2cam" in z.files:
@@ -488,8 +567,10 @@ def load_recording(path: str, video: Optional[str] = None) -> Dict[str, np.ndarr
         if "video" in rec:
             raise ValueError(f"{path}: holds a video key and {video} was given as well; a recording has ONE image source")
         rec["video"] = np.load(video, mmap_mode="r", allow_pickle=False)
-    n = rec["global_orient"].shape[0]
+    n = rec["global_orient"].shape[0] if require_interactee else int(np.asarray(rec["center"]).shape[0])
     _check_frames(rec, n, path)
+    if intrinsics is not None:
+        rec["cam_intrinsics"] = check_intrinsics(intrinsics, n, path)
     want = {"global_orient": [(n, 3)], "body_pose": [(n, 69), (n, 63)], "transl": [(n, 3)], "betas": [(10,)], "wearer_betas": [(10,)],
             "image_feats": [(n, 2048)]}
     if n < 1:
@@ -508,6 +589,8 @@ def load_recording(path: str, video: Optional[str] = None) -> Dict[str, np.ndarr
         raise ValueError(f"{path}: scene_vertices need world2cam: a view is selected per camera pose")
     if "world2cam" in rec:
         check_world2cam(rec["world2cam"], n, path)
+    if not require_interactee:
+        _check_estimate_input(rec, n, path)
     rec["n_frames"] = n
     return rec
 

@@ -89,6 +89,74 @@ def load_backbone_recipe_(module, seed: int = 1234):
     return module
 
 
+def _flow_head_tail(key: str):
+    for mark in ("flow._transform.", "fc_head."):
+        i = key.find(mark)
+        if i >= 0:
+            return key[i:]
+    return None
+
+
+def is_flow_head_key(key: str) -> bool:
+    """Entries of the ProHMR-scene pose head inside a larger model (``proscene.flow.flow._transform...``, ``proscene.flow.fc_head...``)."""
+    return _flow_head_tail(key) is not None
+
+
+def flow_head_recipe_tensor(key: str, shape: Tuple[int, ...], seed: int = 1234) -> np.ndarray:
+    """Recipe of the pose head (SMPLFlow), keyed by the entry's name inside the head (``flow._transform._transforms.2...``,
+    ``fc_head...``; whatever stands in front is dropped, so the module alone and the module inside MLD receive the same values).  The values keep every stage alive and well conditioned: linear weights N(0, 0.03)
+    (``fc_head.layers.2.weight`` N(0, 0.003), so that the camera scale stays near init_cam), biases 0.05 N, BatchNorm weight
+    1 + 0.1 N, bias 0.05 N, running_mean 0.1 N, running_var U(1, 1.3); ActNorm log_scale and shift 0.1 N; LU lower / upper
+    entries 0.02 N, unconstrained_upper_diag 0.1 N, bias 0.05 N; init_cam (0.9, 0, 0) + 0.02 N on the offsets, init_betas 0.1 N."""
+    tail = _flow_head_tail(key)
+    if tail is None:
+        raise KeyError(f"no flow-head recipe for {key}")
+    rng = np.random.Generator(np.random.PCG64(_key_seed(seed, "flow_head." + tail)))
+    shape = tuple(int(s) for s in shape)
+    leaf = tail.rsplit(".", 1)[-1]
+    n = lambda std: std * rng.standard_normal(shape)
+    if leaf == "running_var":
+        out = 1.0 + 0.3 * rng.random(shape)
+    elif leaf == "dummy_buffer":                  # nflows' per-transform device marker: its value is never read
+        out = np.ones(shape)
+    elif leaf == "running_mean":
+        out = n(0.1)
+    elif "batch_norm_layers" in tail and leaf == "weight":
+        out = 1.0 + n(0.1)
+    elif leaf in ("log_scale", "shift", "unconstrained_upper_diag", "init_betas"):
+        out = n(0.1)
+    elif leaf in ("lower_entries", "upper_entries"):
+        out = n(0.02)
+    elif leaf == "init_cam":
+        out = n(0.02)
+        out.reshape(-1)[0] = 0.9
+    elif leaf == "weight" and len(shape) == 2:
+        out = n(0.003 if tail == "fc_head.layers.2.weight" else 0.03)
+    elif leaf == "bias":
+        out = n(0.05)
+    else:
+        raise KeyError(f"no flow-head recipe for {key}")
+    return np.ascontiguousarray(out, dtype=np.float32)
+
+
+def load_flow_head_recipe_(module, seed: int = 1234):
+    """In-place: the flow-head recipe for every floating-point entry of an SMPLFlow-shaped module on its own; the ActNorm
+    ``initialized`` flags become true, the integer buffers stay."""
+    import torch
+
+    sd = module.state_dict()
+    new = {}
+    for k, v in sd.items():
+        if torch.is_floating_point(v):
+            new[k] = torch.from_numpy(flow_head_recipe_tensor(k, tuple(v.shape), seed)).to(dtype=v.dtype)
+        elif v.dtype == torch.bool:
+            new[k] = torch.ones_like(v)
+        else:
+            new[k] = v
+    module.load_state_dict(new, strict=True)
+    return module
+
+
 def recipe_state_dict(shapes: Mapping[str, Iterable[int]], seed: int = 1234) -> Dict[str, np.ndarray]:
     """Fill every entry of ``{name: shape}`` by the recipe."""
     return {k: recipe_tensor(k, tuple(v), seed) for k, v in sorted(shapes.items())}
@@ -104,7 +172,7 @@ def load_recipe_(module, seed: int = 1234):
         if not torch.is_floating_point(v):
             new[k] = v
             continue
-        make = backbone_recipe_tensor if is_backbone_key(k) else recipe_tensor
+        make = flow_head_recipe_tensor if is_flow_head_key(k) else backbone_recipe_tensor if is_backbone_key(k) else recipe_tensor
         new[k] = torch.from_numpy(make(k, tuple(v.shape), seed)).to(dtype=v.dtype)
     module.load_state_dict(new, strict=True)
     return module
