@@ -248,13 +248,19 @@ __device__ __forceinline__ void cl_flag_wait(const int* f, unsigned v) {      //
 // a phase plays the stored waves w % 4 and w % 4 + 4 of the unit -- their 2 x 8 wave-loads with the voff of each, their tiles, per tile the
 // k-blocks in cl_consume's order -- so every sum is the one the eight-wave schedule formed.  Ring: 2 slots x 16 wave-loads per wave.
 //   G0  slot 0: A0 -> C -> next A0      slot 1: A1 -> E -> next A1          G1  slot 0: B -> F0      slot 1: D -> F1
-//   X1 published: B (G1) | X1 swept: C (G0) | phase B: E (G0) | X2 published: D (G1) | X2 swept: F0 (G1) | phase D: next A0 (G0) |
+//   X1 published: B (G1) | X1 first poll issued: E, half (G0) | X1 swept: C (G0) | phase B: E, half (G0) | X2 published: D (G1) |
+//   X2 swept: F0 (G1) | phase D: next A0 (G0) |
 //   phase E + ffn epilogue: F1 in halves (G1) | phase F: next A1 (G0; the skip half, wanted in skip layers only)
 // Nothing is requested ahead of a publish (phases A and C end in granule stores), every slot is requested only after its unit was consumed,
 // and but for B and A1 -- their slots hold F0 / E until late, and phase A may not request -- every unit is at least a phase ahead.
-// The barrier that ends a phase waits for the requesting group too: 64 wave-loads are 1 k cycles of the address path, a whole unit per phase
-// fits B, D and F but not E.  Stamps of this schedule and of the one before: profiles/cluster_wave_groups.txt.
-// The epilogue wave requests nothing between a publish and the end of its sweep: its polls stand behind no load of its own.
+// The barrier that ends a phase waits for the requesting group too: 64 wave-loads are 1 k cycles of the address path, and the 16 MFMAs of B, D
+// or E take 0.55 - 0.6 k: a whole unit per phase makes D last as long as the request (1.0 k), as it made B (0.9 k); half a unit is hidden.
+// The other half of E travels behind the FIRST poll of X1 (FPI below): between a publish and the end of its sweep the epilogue wave requests
+// that half unit and nothing else, so its first poll stands behind no load, a repeated one behind 32 wave-loads.  (The same for the next A0
+// behind X2's first poll was built and measured: 0.008 ms of the pass on top of this, 1.1 - 1.25 x the run-to-run spread, taken out again.)
+// DCL_POLL_SLEEP matters since then -- measured at B = 32, and at 12 also at B = 8: at 10 and below the first poll stands in G1's unit B and
+// the pass loses what it gained and more, 12 .. 16 measure the same, at 20 the gain is gone.  Stamps: profiles/cluster_wave_groups.txt,
+// profiles/cluster_poll_windows.txt.
 template <typename WT, int C, bool Q> struct ClGrp { static constexpr bool ON = C == 8 && WT::MFMA && !Q; };
 struct ClSchedGrp { static constexpr bool WIN = true; static constexpr int PRO = 0; typedef ClSeq<> W1A, W1B, W2A, W2B, WXA, WXB, W3, AF; };   // (the windows and their flags stay; what goes out in them is listed above)
 struct ClRing2 { u32x4 r[2][2][8]; };              // [slot][stored wave w % 4 | w % 4 + 4][wave-load]
@@ -552,6 +558,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
     int* FLG = reinterpret_cast<int*>(RES + 256);   // [4]
     float* COEF = RES + 256 + 4;                 // (GRP) [8]   the step's scheduler coefficients (+ 4 spare), see ClRowG
     float* NZ = COEF + 12;                       // (GRP) [256] the sample's step noise
+    int* FPI = reinterpret_cast<int*>(COEF + 8); // (GRP) "first poll issued": the exchange's epoch (the first of COEF's spare words; FLG has none)
     constexpr int XZERO = 512 + 512 + 2 * (G::NB > 128 ? G::NB : 128) + 1024;
 
     const __amdgpu_buffer_rsrc_t wg = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ka.wgc), 0, (int)ka.wgc_bytes, 0x00020000);
@@ -579,6 +586,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
     else stage_dma<1, Q, 0, 0>(wave, lane, STG, vp, &lay->L[0], A.ttab + (size_t)row * SEEME_TROW, 0, A, b, N, 0, ca_R);
     for (int i = tid; i < XZERO / 4; i += DEN_THREADS) st4(XA + 4 * i, make_float4(0.f, 0.f, 0.f, 0.f));
     if (tid >= 1 && tid < 4) FLG[tid] = 0;                   // window flags (epochs are never 0)
+    if constexpr (GRP) { if (tid == 4) FPI[0] = 0; }
     bool dead = false, local = false;
     if (epi) {
         // first exchange, always write-through: the XCC id of every workgroup of the cluster (HW_REG_XCC_ID, bits 3:0)
@@ -606,7 +614,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
     }
     ClRing<WT> ring;
     ClRing2 gr;                                  // (GRP)
-    (void)gr; (void)gvoff; (void)w4; (void)COEF; (void)NZ;
+    (void)gr; (void)gvoff; (void)w4; (void)COEF; (void)NZ; (void)FPI;
     if constexpr (GRP) {
         if (wave < 4) {       // layer 0 has no skip linear; A1 is requested all the same (nowhere), as after every phase F: one count of loads in flight at a layer's start
             clg_issue<0>(gr, gvoff, wg, (unsigned)(c * G::NU + G::U_A) * W::UNIT_BYTES, true, w4 < 2);
@@ -828,7 +836,34 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
                 u32x4 gv0, gv1, gy0, gy1, gs[G::SC / 2];
                 gy0 = gy1 = u32x4{0u, epoch, 0u, epoch};
                 unsigned spins = 0;
-                for (;;) {
+                bool swept = false;
+                if constexpr (GRP) {
+                    // The FIRST poll, peeled: behind its loads the vector-memory path has nothing to do until they return, and waves 1 .. 3 spin.
+                    // The first half of unit E (stored waves 0 .. 3) goes out in that flight time -- this wave's share first (behind the others' it
+                    // would wait out their backlog), then the release of waves 1 .. 3 (FPI) -- and the poll is checked with the loads still in
+                    // flight: the poll's are the older ones, vmcnt(8 + ...).  (The loads and the check stand here and in the loop below in full: shared
+                    // through lambdas, every instantiation's poll loop compiled differently -- five-fold unrolled, five more vmcnt(0).)  A poll that has to be repeated stands behind them (and waits with
+                    // vmcnt(0)), which is why only half a unit travels here: the whole unit cost X1 0.7 k cycles for 0.35 k off phase B, the half
+                    // 0.2 k for 0.35 k (profiles/cluster_poll_windows.txt); the other half stays in phase B, which hides 32 wave-loads.
+                    gv0 = __builtin_amdgcn_raw_buffer_load_b128(xr_, o_v, 0, 16);
+                    gv1 = __builtin_amdgcn_raw_buffer_load_b128(xr_, o_v + 16, 0, 16);
+                    if (skip) {
+                        gy0 = __builtin_amdgcn_raw_buffer_load_b128(xr_, o_v + G::S * 8, 0, 16);
+                        gy1 = __builtin_amdgcn_raw_buffer_load_b128(xr_, o_v + G::S * 8 + 16, 0, 16);
+                    }
+#pragma unroll
+                    for (int j = 0; j < G::SC / 2; ++j) gs[j] = __builtin_amdgcn_raw_buffer_load_b128(xr_, o_s + 16 * j, 0, 16);
+                    __builtin_amdgcn_sched_barrier(0);
+                    clg_issue<1, 1>(gr, gvoff, wg, bc + (unsigned)G::U_E * W::UNIT_BYTES, true, true);
+                    if (lane == 0) cl_flag_set(FPI, e1);
+                    __builtin_amdgcn_sched_barrier(0);
+                    unsigned ok = cl_tags_ok(gv0, epoch) & cl_tags_ok(gv1, epoch) & cl_tags_ok(gy0, epoch) & cl_tags_ok(gy1, epoch);
+#pragma unroll
+                    for (int j = 0; j < G::SC / 2; ++j) ok &= cl_tags_ok(gs[j], epoch);
+                    swept = __all(ok != 0u) || dead;
+                    asm volatile("" ::: "memory");      // (a later poll reads the granules again)
+                }
+                if (!swept) for (;;) {
                     gv0 = __builtin_amdgcn_raw_buffer_load_b128(xr_, o_v, 0, 16);
                     gv1 = __builtin_amdgcn_raw_buffer_load_b128(xr_, o_v + 16, 0, 16);
                     if (skip) {
@@ -888,6 +923,10 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
                 }
                 if constexpr (WIN) {
                     cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W1A{});
+                    if constexpr (GRP) {     // the first poll is on its way: E's first half into its flight time (slot 1: phase A has consumed A1)
+                        cl_flag_wait(FPI, e1);
+                        clg_issue<1, 1>(gr, gvoff, wg, bc + (unsigned)G::U_E * W::UNIT_BYTES, true, true);
+                    }
                     cl_flag_wait(FLG + 2, e1);
                     cl_issue_seq<WT, C, Q>(ring, wave, voff, wg, bc, bn, skip, nskip, typename SCH::W1B{});
                     if constexpr (GRP) clg_issue<0>(gr, gvoff, wg, bc + (unsigned)G::U_C * W::UNIT_BYTES, true, true);
@@ -902,8 +941,8 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
             //  of the phase -- BEFORE the deferred re-fills: vmcnt is in order, and the store must not wait for them)
             if constexpr (Q) nxt.load(0, wave, lane, vp, Ln, tt_next, ln, A, b, c, ca_next, ca_R);
             if constexpr (!WIN) cl_refills<WT, C, Q, G::U_A + A_DEF0>(ring, wave, voff, wg, bc, bn, skip, nskip, std::make_integer_sequence<int, 2 * G::TA - A_DEF0>{});   // slots of stage A
-            if constexpr (GRP) {      // (G1 computes; this group requests E)
-                clg_issue<1>(gr, gvoff, wg, bc + (unsigned)G::U_E * W::UNIT_BYTES, true, true);
+            if constexpr (GRP) {      // (G1 computes; this group requests E's second half: the first went out behind X1's first poll)
+                clg_issue<1, 2>(gr, gvoff, wg, bc + (unsigned)G::U_E * W::UNIT_BYTES, true, true);
             } else {
                 f32x4 acc[G::TB];
                 cl_zero<G::TB>(acc);
