@@ -197,6 +197,15 @@ int seeme_denoiser_ca_tables(const SeemeDenoiserWeights* w, const float* ctab, c
                              int trow_per_sample, int n_trow, int Bc, float* catab,
                              void* workspace, size_t ws_bytes, void* stream);
 
+/* ONE condition token: seeme_denoiser_cond_tables + seeme_denoiser_ca_tables as ONE launch, for cond [Bc,1,256].  Each
+ * workgroup of a catab tile forms the value columns of its samples itself, so ctab and catab come out of one grid with the
+ * bits of the two calls (same MFMAs, operands and k order per element) and no workspace.  `zero` (optional, 16-byte aligned):
+ * zero_bytes bytes that the same launch sets to zero -- the exchange buffer of a cluster launch that follows on `stream`
+ * (SeemeDenCluster.xchg_zeroed). */
+int seeme_denoiser_tables1(const SeemeDenoiserWeights* w, const float* cond, const float* ttab, const int32_t* trow,
+                           int trow_per_sample, int n_trow, int Bc, float* ctab, float* catab,
+                           void* zero, size_t zero_bytes, void* stream);
+
 typedef struct {
     int B;                 /* samples (latents rows) */
     int N;                 /* condition tokens per sample */
@@ -235,7 +244,7 @@ int seeme_denoiser_sample(const SeemeDenoiserWeights* w, const SeemeSampleArgs* 
  *         (seeme_amd/mld_denoiser.py, geometry from seeme_den_cluster_layout); the skip linears of layers 3, 4 are folded
  *         into that layer's in_proj;
  *   vpc : the vector array of seeme_den_layout() order with in_b of layers 3, 4 = W_in' b_skip + b_in';
- *   xchg: exchange workspace (>= seeme_den_cluster_xchg_bytes(B, C), 16-byte aligned), zeroed by the call on `stream`.  Word 0
+ *   xchg: exchange workspace (>= seeme_den_cluster_xchg_bytes(B, C), 16-byte aligned), zeroed by the call on `stream` (unless xchg_zeroed).  Word 0
  *         of it is non-zero after the launch if a cluster gave up waiting for a peer (results invalid), word 1 counts the
  *         clusters that ran with L2-local granule stores.
  *   placement 0: the workgroups of a cluster have equal blockIdx % 8 (one XCD under round-robin dispatch), 1: consecutive
@@ -254,6 +263,9 @@ typedef struct {
                                           * (two or four MFMA A rows per sample, wave s = epilogue wave of sample s): fp16 image (C = 4 or 8) or bf16
                                           * image (C = 4, at most 4 samples), one or two condition tokens, one table row per step; ceil(B / samples) rounded up to 8 clusters x C <= CUs;
                                           * xchg >= seeme_den_cluster_ms_xchg_bytes(B, C, samples) */
+    int xchg_zeroed;                     /* 1: the caller zeroed the first seeme_den_cluster[_ms]_xchg_bytes(...) bytes of xchg on `stream`
+                                          * after the previous cluster launch (seeme_denoiser_tables1 does): the call skips its own
+                                          * memset.  0: the call zeroes them */
 } SeemeDenCluster;
 size_t seeme_den_cluster_xchg_bytes(int B, int C);
 size_t seeme_den_cluster_ms_xchg_bytes(int B, int C, int samples);

@@ -1312,7 +1312,7 @@ extern "C" int seeme_den_cluster_layout(int C, int wdtype, int query, int64_t* o
 }
 
 template <typename WT, int C, bool Q>
-static int launch_den_cluster(const ClArgs& ka0, hipStream_t st) {
+static int launch_den_cluster(const ClArgs& ka0, hipStream_t st, bool zeroed) {
     ClArgs ka = ka0;
     ka.clusters = (ka.s.B + 7) / 8 * 8;
     const int grid = ka.clusters * C;
@@ -1326,19 +1326,19 @@ static int launch_den_cluster(const ClArgs& ka0, hipStream_t st) {
     if (lds > 160 * 1024 || lds <= 80 * 1024) return seeme_fail("denoiser_sample_cluster: LDS footprint must force one workgroup per CU");
     SEEME_HIP(hipFuncSetAttribute((const void*)k_den_cluster<WT, C, Q>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // granules and header are zeroed before EVERY launch (tags of an earlier launch must never match)
-    SEEME_HIP(hipMemsetAsync(ka.hdr, 0, seeme_den_cluster_xchg_bytes(ka.s.B, C), st));
+    if (!zeroed) SEEME_HIP(hipMemsetAsync(ka.hdr, 0, seeme_den_cluster_xchg_bytes(ka.s.B, C), st));
     hipLaunchKernelGGL((k_den_cluster<WT, C, Q>), dim3(grid), dim3(DEN_THREADS), lds, st, ka);
     return seeme_check_launch("k_den_cluster");
 }
 template <typename WT>
-static int launch_den_cluster_c(const ClArgs& ka, int C, bool q, hipStream_t st) {
-    if (C == 8) return q ? launch_den_cluster<WT, 8, true>(ka, st) : launch_den_cluster<WT, 8, false>(ka, st);
-    if (C == 4) return q ? launch_den_cluster<WT, 4, true>(ka, st) : launch_den_cluster<WT, 4, false>(ka, st);
-    if (C == 2) return q ? launch_den_cluster<WT, 2, true>(ka, st) : launch_den_cluster<WT, 2, false>(ka, st);
+static int launch_den_cluster_c(const ClArgs& ka, int C, bool q, hipStream_t st, bool zeroed) {
+    if (C == 8) return q ? launch_den_cluster<WT, 8, true>(ka, st, zeroed) : launch_den_cluster<WT, 8, false>(ka, st, zeroed);
+    if (C == 4) return q ? launch_den_cluster<WT, 4, true>(ka, st, zeroed) : launch_den_cluster<WT, 4, false>(ka, st, zeroed);
+    if (C == 2) return q ? launch_den_cluster<WT, 2, true>(ka, st, zeroed) : launch_den_cluster<WT, 2, false>(ka, st, zeroed);
     return seeme_fail("denoiser_sample_cluster: C must be 2, 4 or 8");
 }
 
-static int den_cluster_ms_dispatch(const SeemeDenoiserWeights* w, const SeemeDenCluster* cl, const SeemeSampleArgs* a, ClArgs& ka, hipStream_t st);   // den_cluster_ms.inc.hip
+static int den_cluster_ms_dispatch(const SeemeDenoiserWeights* w, const SeemeDenCluster* cl, const SeemeSampleArgs* a, ClArgs& ka, hipStream_t st, bool zeroed);   // den_cluster_ms.inc.hip
 
 extern "C" int seeme_denoiser_sample_cluster(const SeemeDenoiserWeights* w, const SeemeDenCluster* cl, const SeemeSampleArgs* a, void* stream) {
     if (a->B <= 0) return seeme_fail("denoiser_sample_cluster: B must be > 0");
@@ -1365,9 +1365,10 @@ extern "C" int seeme_denoiser_sample_cluster(const SeemeDenoiserWeights* w, cons
     ka.xg = (unsigned long long*)((char*)cl->xchg + DCL_HDR_BYTES);
     ka.placement = cl->placement; ka.flags = cl->flags; ka.clusters = 0; ka.spc = 1;
     hipStream_t st = (hipStream_t)stream;
-    if (ms) return den_cluster_ms_dispatch(w, cl, a, ka, st);
-    if (cl->wdtype == 0) return launch_den_cluster_c<WF32>(ka, cl->C, q, st);
-    if (cl->wdtype == 1) return launch_den_cluster_c<WBF16>(ka, cl->C, q, st);
-    if (cl->wdtype == 2) return launch_den_cluster_c<WF16>(ka, cl->C, q, st);
+    const bool zeroed = cl->xchg_zeroed != 0;     // the caller zeroed granules and header on this stream (seeme_denoiser_tables1)
+    if (ms) return den_cluster_ms_dispatch(w, cl, a, ka, st, zeroed);
+    if (cl->wdtype == 0) return launch_den_cluster_c<WF32>(ka, cl->C, q, st, zeroed);
+    if (cl->wdtype == 1) return launch_den_cluster_c<WBF16>(ka, cl->C, q, st, zeroed);
+    if (cl->wdtype == 2) return launch_den_cluster_c<WF16>(ka, cl->C, q, st, zeroed);
     return seeme_fail("denoiser_sample_cluster: wdtype must be 0 (fp32), 1 (bf16) or 2 (fp16)");
 }

@@ -807,7 +807,7 @@ extern "C" size_t seeme_den_cluster_ms_xchg_bytes(int B, int C, int spc) {      
 }
 
 template <typename WT, int C, bool Q, bool NARROW>
-static int launch_den_cluster_ms(const ClArgs& ka0, hipStream_t st) {
+static int launch_den_cluster_ms(const ClArgs& ka0, hipStream_t st, bool zeroed) {
     ClArgs ka = ka0;
     ka.clusters = clm_clusters(ka.s.B, ka.spc);
     const int grid = ka.clusters * C;
@@ -819,13 +819,13 @@ static int launch_den_cluster_ms(const ClArgs& ka0, hipStream_t st) {
     const size_t lds = (size_t)ClM<WT, C, Q, NARROW>::LDS_FLOATS * sizeof(float);
     if (lds > 160 * 1024 || lds <= 80 * 1024) return seeme_fail("denoiser_sample_cluster: LDS footprint must force one workgroup per CU");
     SEEME_HIP(hipFuncSetAttribute((const void*)k_den_cluster_ms<WT, C, Q, NARROW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SEEME_HIP(hipMemsetAsync(ka.hdr, 0, seeme_den_cluster_ms_xchg_bytes(ka.s.B, C, ka.spc), st));
+    if (!zeroed) SEEME_HIP(hipMemsetAsync(ka.hdr, 0, seeme_den_cluster_ms_xchg_bytes(ka.s.B, C, ka.spc), st));
     hipLaunchKernelGGL((k_den_cluster_ms<WT, C, Q, NARROW>), dim3(grid), dim3(DEN_THREADS), lds, st, ka);
     return seeme_check_launch("k_den_cluster_ms");
 }
 
 // called by seeme_denoiser_sample_cluster when SeemeDenCluster.samples > 1
-static int den_cluster_ms_dispatch(const SeemeDenoiserWeights* w, const SeemeDenCluster* cl, const SeemeSampleArgs* a, ClArgs& ka, hipStream_t st) {
+static int den_cluster_ms_dispatch(const SeemeDenoiserWeights* w, const SeemeDenCluster* cl, const SeemeSampleArgs* a, ClArgs& ka, hipStream_t st, bool zeroed) {
     if (cl->wdtype != 2 && cl->wdtype != 1) return seeme_fail("denoiser_sample_cluster: several samples per cluster need a 16-bit weight image");
     if (cl->C != 4 && cl->C != 8) return seeme_fail("denoiser_sample_cluster: several samples per cluster need C = 4 or 8");
     if (cl->samples > 8) return seeme_fail("denoiser_sample_cluster: at most 8 samples per cluster");
@@ -835,10 +835,10 @@ static int den_cluster_ms_dispatch(const SeemeDenoiserWeights* w, const SeemeDen
     ka.spc = cl->samples;
     if (cl->wdtype == 1) {      // bf16 image: four A rows per sample, up to 4 samples per cluster (4-CU clusters only)
         if (cl->C != 4) return seeme_fail("denoiser_sample_cluster: the bf16 image takes several samples per cluster at C = 4 only");
-        return a->N == 2 ? launch_den_cluster_ms<WBF16, 4, true, false>(ka, st) : launch_den_cluster_ms<WBF16, 4, false, false>(ka, st);
+        return a->N == 2 ? launch_den_cluster_ms<WBF16, 4, true, false>(ka, st, zeroed) : launch_den_cluster_ms<WBF16, 4, false, false>(ka, st, zeroed);
     }
     if (cl->C == 4 && cl->samples <= 4)      // fp16, at most four samples per cluster: four A rows per sample, one sample per lane group
-        return a->N == 2 ? launch_den_cluster_ms<WF16, 4, true, false>(ka, st) : launch_den_cluster_ms<WF16, 4, false, false>(ka, st);
-    if (a->N == 2) return cl->C == 8 ? launch_den_cluster_ms<WF16, 8, true, true>(ka, st) : launch_den_cluster_ms<WF16, 4, true, true>(ka, st);
-    return cl->C == 8 ? launch_den_cluster_ms<WF16, 8, false, true>(ka, st) : launch_den_cluster_ms<WF16, 4, false, true>(ka, st);
+        return a->N == 2 ? launch_den_cluster_ms<WF16, 4, true, false>(ka, st, zeroed) : launch_den_cluster_ms<WF16, 4, false, false>(ka, st, zeroed);
+    if (a->N == 2) return cl->C == 8 ? launch_den_cluster_ms<WF16, 8, true, true>(ka, st, zeroed) : launch_den_cluster_ms<WF16, 4, true, true>(ka, st, zeroed);
+    return cl->C == 8 ? launch_den_cluster_ms<WF16, 8, false, true>(ka, st, zeroed) : launch_den_cluster_ms<WF16, 4, false, true>(ka, st, zeroed);
 }

@@ -1121,6 +1121,260 @@ extern "C" int seeme_denoiser_ca_tables(const SeemeDenoiserWeights* w, const flo
     return seeme_launch_linear(ka, st);
 }
 
+// ------------------------------------------------------------------ ctab and catab for ONE condition token in ONE launch
+// The three launches above (cond tables, k_ca_rows, proj_out) depend on each other through 256 ctab columns per (sample, layer)
+// only, so a workgroup that owns one 32-row tile of catab rows for one layer forms those columns itself and no workgroup waits
+// for another.  Block indices, long workgroups first:
+//   [0, ca)        : ca tiles (32-row tile of rows = Bc R, layer l): value rows of the tile's samples -> row transform -> proj_out;
+//   [ca, ca + ct)  : the narrow-form tiles of seeme_denoiser_cond_tables (z = 0, 1), unchanged arithmetic;
+//   [ca + ct, ...) : 16-byte zero stores over an optional region (the cluster kernels' exchange buffer).
+// Every output element sees the MFMAs, operands and k order of the three launches: ctab and catab are the same bits.
+struct Tables1Args {
+    const float* cond; const float* ttab; const int32_t* trow; int per_sample, n_trow, R, rows, Bc;
+    const float* kv_w; const float* kv_b; const float* cf_w; const float* cf_b; const float* ln_w; const float* ln_b;
+    const float* pn_w; const float* pn_b; const float* po_w; const float* po_b;
+    float* ctab; float* catab; unsigned char* zero; size_t zero_bytes;
+    int ca_blocks, ct_blocks, zero_blocks;
+};
+#define T1_LD (256 + LDS_PAD)
+// rows b0 .. b0 + n - 1 of cond [Bc,256] into As[32][T1_LD] (zero rows beyond), all 8 loads of a thread in flight together; with
+// `ln` the pre-LayerNorm of k_linear (affine ln_w / ln_b, K = 256) over the staged rows
+__device__ __forceinline__ void t1_stage_cond(float* __restrict__ As, const float* __restrict__ cond, int b0, int n, bool ln,
+                                              const float* __restrict__ ln_w, const float* __restrict__ ln_b, int tid) {
+    const int wave = tid >> 6, lane = tid & 63;
+    const bool vec = (reinterpret_cast<size_t>(cond) & 15) == 0;
+    float lw[4], lb[4];         // the LayerNorm affine of this lane's columns, requested with the rows (read in the row loop it is one more round trip)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { lw[k] = ln_w[lane + 64 * k]; lb[k] = ln_b[lane + 64 * k]; }
+    float4 v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int row = 4 * j + wave;
+        const bool ok = row < n;
+        const float* p = ok ? cond + (size_t)(b0 + row) * 256 + 4 * lane : cond;
+        v[j] = vec ? ld4(p) : make_float4(p[0], p[1], p[2], p[3]);
+        if (!ok) v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) st4(As + (4 * j + wave) * T1_LD + 4 * lane, v[j]);
+    __syncthreads();
+    if (ln) {
+        for (int rr = 0; rr < 8; ++rr) {
+            const int row = wave * 8 + rr;
+            if (row >= n) break;   // wave-uniform; a zero row stays zero
+            float s = 0.f;
+            for (int c = lane; c < 256; c += 64) s += As[row * T1_LD + c];
+            const float mean = wave_sum(s) / 256.f;
+            float q = 0.f;
+            for (int c = lane; c < 256; c += 64) { float d = As[row * T1_LD + c] - mean; q += d * d; }
+            const float rs = 1.f / sqrtf(wave_sum(q) / 256.f + 1e-5f);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int c = lane + 64 * k;
+                As[row * T1_LD + c] = (As[row * T1_LD + c] - mean) * rs * lw[k] + lb[k];
+            }
+        }
+        __syncthreads();
+    }
+}
+// One row of k_ca_rows: SiLU(AdaLN(LN(v))).  The arithmetic of wave_ln and f4_adaln with the contractions hipcc makes in k_ca_rows
+// spelled out (var / 256 + eps, LN affine and AdaLN are one fma each, the sum of squares is not fused) and contraction off:
+// inlined into this kernel the same source came out as mul + add, and the table has to be the same bits.
+__device__ __forceinline__ float4 t1_ca_row(float4 v, float4 wv, float4 bv, float4 scl, float4 shf) {
+#pragma clang fp contract(off)
+    const float mean = wave_sum(v.x + v.y + v.z + v.w) * (1.f / 256.f);
+    const float4 c = make_float4(v.x - mean, v.y - mean, v.z - mean, v.w - mean);
+    const float xx = c.x * c.x, yy = c.y * c.y, zz = c.z * c.z, ww = c.w * c.w;
+    const float rs = fast_rsq(__builtin_fmaf(wave_sum(xx + yy + zz + ww), 1.f / 256.f, 1e-5f));
+    const float4 t = make_float4(c.x * rs, c.y * rs, c.z * rs, c.w * rs);
+    const float4 hn = make_float4(__builtin_fmaf(wv.x, t.x, bv.x), __builtin_fmaf(wv.y, t.y, bv.y), __builtin_fmaf(wv.z, t.z, bv.z), __builtin_fmaf(wv.w, t.w, bv.w));
+    const float4 one = make_float4(1.f + scl.x, 1.f + scl.y, 1.f + scl.z, 1.f + scl.w);
+    return f4_silu(make_float4(__builtin_fmaf(hn.x, one.x, shf.x), __builtin_fmaf(hn.y, one.y, shf.y), __builtin_fmaf(hn.z, one.z, shf.z), __builtin_fmaf(hn.w, one.w, shf.w)));
+}
+// tile_gemm_f32 at K = 256 against 256 whole rows of W (ldw 256), split in two: t1_prime requests the first four k-blocks of the
+// wave's four column tiles, t1_gemm256 runs the k-blocks -- the MFMAs, operands and order of tile_gemm_f32's unrolled K16 == 16
+// path.  Between the two the caller does work that does not need W (staging, the row transform), so W's latency passes behind it.
+struct T1Ring { float4 br[4][4]; };
+__device__ __forceinline__ void t1_prime(T1Ring& R, const float* __restrict__ W, int n0) {
+    const int lane = threadIdx.x & 63, r = lane & 15, kq = lane >> 4;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) R.br[u][nt] = ld4(W + ((unsigned)(n0 + nt * 16 + r) * 256u + 4u * kq + u * 16u));
+}
+template <int MTL>
+__device__ __forceinline__ void t1_gemm256(const float* __restrict__ As, const float* __restrict__ W, int n0, T1Ring& R, f32x4 (&acc)[MTL][4]) {
+    const int lane = threadIdx.x & 63, r = lane & 15, kq = lane >> 4;
+    unsigned wo[4];                   // 32-bit offsets from the uniform base: half the address registers of four pointers
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) wo[nt] = (unsigned)(n0 + nt * 16 + r) * 256u + 4u * kq;
+    const float* ap = As + r * T1_LD + 4 * kq;
+#pragma unroll
+    for (int kb = 0; kb < 16; ++kb) {
+        const int u = kb & 3;
+        float4 av[MTL], b[4];
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) b[nt] = R.br[u][nt];
+#pragma unroll
+        for (int mt = 0; mt < MTL; ++mt) av[mt] = ld4(ap + mt * 16 * T1_LD + kb * 16);
+        if (kb < 12) {      // the slot is re-filled above this k-block's MFMAs (see tile_gemm_f32)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) R.br[u][nt] = ld4(W + (wo[nt] + (kb + 4) * 16u));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int mt = 0; mt < MTL; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt].x, b[nt].x, acc[mt][nt], 0, 0, 0);
+#pragma unroll
+        for (int mt = 0; mt < MTL; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt].y, b[nt].y, acc[mt][nt], 0, 0, 0);
+#pragma unroll
+        for (int mt = 0; mt < MTL; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt].z, b[nt].z, acc[mt][nt], 0, 0, 0);
+#pragma unroll
+        for (int mt = 0; mt < MTL; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt].w, b[nt].w, acc[mt][nt], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+__device__ __forceinline__ void t1_store4(float* __restrict__ yp, float4 v, bool vec) {
+    if (vec) st4(yp, v);
+    else { yp[0] = v.x; yp[1] = v.y; yp[2] = v.z; yp[3] = v.w; }
+}
+__global__ __launch_bounds__(256, 2) void k_den_tables1(const Tables1Args a) {
+    extern __shared__ __attribute__((aligned(16))) float t1_smem[];
+    float* As = t1_smem;                    // [32][264]
+    float* Cs = t1_smem + TILE_M * T1_LD;   // [32][264]
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    int bid = blockIdx.x;
+    if (bid < a.ca_blocks) {
+        const int l = bid % SEEME_DEN_NL, m0 = (bid / SEEME_DEN_NL) * TILE_M;
+        const int mlast = m0 + TILE_M - 1 < a.rows ? m0 + TILE_M - 1 : a.rows - 1;
+        const int bc_lo = m0 / a.R, ns = mlast / a.R - bc_lo + 1;          // the tile's samples: at most 32
+        // The table rows of the wave's 8 output rows in ONE load: lane j < 8 holds (sample, trow entry) of row j, handed round by
+        // readlane.  It is the oldest load in flight, so the wait for it leaves everything requested behind it in flight: the first
+        // fragments of the value rows of ca_fold_w, the bias and proj_out.norm.  (Eight loads in the row loop were eight round trips.)
+        const int ml = m0 + wave * 8 + (lane & 7), mlc = ml < a.rows ? ml : m0;       // rows beyond the table: row m0, the result is dropped
+        const int bcl = mlc / a.R, rl = mlc - bcl * a.R;
+        const int trl = a.trow[a.per_sample ? bcl % a.n_trow : rl];
+        const float* Wv = a.cf_w + (size_t)(l * 512 + 256) * 256;
+        const float* Wo = a.po_w + (size_t)l * 256 * 256;
+        T1Ring ring;
+        t1_prime(ring, Wv, wave * 64);
+        const BiasRegs<4> bias_v = bias_load<4>(a.cf_b + l * 512 + 256, wave * 64, 256);
+        const float4 pnw = ld4(a.pn_w + l * 256 + 4 * lane), pnb = ld4(a.pn_b + l * 256 + 4 * lane);
+        float4 tsc[8], tsh[8];
+        int srow[8];                        // row of the value tile (sample - bc_lo) of each output row
+        const float* ttp[8];                // its (scale | shift) row; rows 0 .. 3 are requested here, 4 .. 7 behind the value GEMM (registers)
+#pragma unroll
+        for (int rr = 0; rr < 8; ++rr) {
+            ttp[rr] = a.ttab + (size_t)__builtin_amdgcn_readlane(trl, rr) * SEEME_TROW + 2560 + l * 1024;
+            srow[rr] = __builtin_amdgcn_readlane(bcl, rr) - bc_lo;
+            if (rr < 4) { tsc[rr] = ld4(ttp[rr] + 4 * lane); tsh[rr] = ld4(ttp[rr] + 256 + 4 * lane); }
+        }
+        t1_stage_cond(As, a.cond, bc_lo, ns, true, a.ln_w, a.ln_b, tid);
+        // value_l of the tile's samples: columns 2560 + 512 l + 256 .. of ctab, kept in LDS
+        if (ns <= 16) {
+            f32x4 acc[1][4];
+            acc_zero(acc);
+            t1_gemm256<1>(As, Wv, wave * 64, ring, acc);
+            acc_store_lds<1, 4>(acc, Cs, T1_LD, wave * 64, bias_v, SEEME_ACT_NONE);
+        } else {
+            f32x4 acc[2][4];
+            acc_zero(acc);
+            t1_gemm256<2>(As, Wv, wave * 64, ring, acc);
+            acc_store_lds<2, 4>(acc, Cs, T1_LD, wave * 64, bias_v, SEEME_ACT_NONE);
+        }
+#pragma unroll
+        for (int rr = 4; rr < 8; ++rr) { tsc[rr] = ld4(ttp[rr] + 4 * lane); tsh[rr] = ld4(ttp[rr] + 256 + 4 * lane); }   // arrive behind rows 0 .. 3 of the transform
+        t1_prime(ring, Wo, wave * 64);      // proj_out's first fragments: their latency passes behind the row transform
+        const BiasRegs<4> bias_o = bias_load<4>(a.po_b + l * 256, wave * 64, 256);
+        __syncthreads();
+        // row transform of k_ca_rows into the A tile (rows beyond the table: zero, as k_linear stages them); no branch, so that the
+        // eight rows' reductions interleave
+#pragma unroll
+        for (int rr = 0; rr < 8; ++rr) {
+            const int row = wave * 8 + rr;
+            float4 o = t1_ca_row(ld4(Cs + srow[rr] * T1_LD + 4 * lane), pnw, pnb, tsc[rr], tsh[rr]);
+            if (m0 + row >= a.rows) o = make_float4(0.f, 0.f, 0.f, 0.f);
+            st4(As + row * T1_LD + 4 * lane, o);
+            if (rr == 3) __builtin_amdgcn_sched_barrier(0);     // four rows at a time: all eight interleaved spill registers
+        }
+        __syncthreads();
+        f32x4 acc[2][4];
+        acc_zero(acc);
+        t1_gemm256<2>(As, Wo, wave * 64, ring, acc);
+        acc_store_lds<2, 4>(acc, Cs, T1_LD, wave * 64, bias_o, SEEME_ACT_NONE);
+        __syncthreads();
+        const bool vec = (reinterpret_cast<size_t>(a.catab) & 15) == 0;
+#pragma unroll
+        for (int rr = 0; rr < 8; ++rr) {
+            const int row = wave * 8 + rr, m = m0 + row;
+            if (m >= a.rows) continue;   // wave-uniform
+            t1_store4(a.catab + ((size_t)m * SEEME_DEN_NL + l) * 256 + 4 * lane, ld4(Cs + row * T1_LD + 4 * lane), vec);
+        }
+        return;
+    }
+    bid -= a.ca_blocks;
+    if (bid < a.ct_blocks) {
+        const int by = bid % 40, z = (bid / 40) & 1, m0 = (bid / 80) * TILE_M, cn0 = by * 64;
+        const int n = a.Bc - m0 < TILE_M ? a.Bc - m0 : TILE_M;
+        t1_stage_cond(As, a.cond, m0, n, z == 1, a.ln_w, a.ln_b, tid);
+        f32x4 acc[2][1];
+        acc_zero(acc);
+        tile_gemm_f32<2, 1>(As, T1_LD, z ? a.cf_w : a.kv_w, 256, cn0 + wave * 16, 2560, 16, acc);
+        acc_store_lds<2, 1>(acc, Cs, T1_LD, wave * 16, z ? a.cf_b : a.kv_b, cn0, 2560, SEEME_ACT_NONE);
+        __syncthreads();
+        if (lane >= 16) return;
+        const bool vec = (reinterpret_cast<size_t>(a.ctab) & 15) == 0;
+#pragma unroll
+        for (int rr = 0; rr < 8; ++rr) {
+            const int row = wave * 8 + rr, m = m0 + row;
+            if (m >= a.Bc) continue;
+            t1_store4(a.ctab + (size_t)m * SEEME_CROW + z * 2560 + cn0 + 4 * lane, ld4(Cs + row * T1_LD + 4 * lane), vec);
+        }
+        return;
+    }
+    bid -= a.ct_blocks;
+    // zero region: 16-byte vector stores, grid-stride over the zero blocks; the last bytes of a length that is no multiple of 16 singly
+    const size_t n16 = a.zero_bytes >> 4;
+    uint4* z16 = reinterpret_cast<uint4*>(a.zero);
+    for (size_t i = (size_t)bid * 256 + tid; i < n16; i += (size_t)a.zero_blocks * 256) z16[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (bid == 0 && (size_t)tid < (a.zero_bytes & 15)) a.zero[(n16 << 4) + tid] = 0;
+}
+
+extern "C" int seeme_denoiser_tables1(const SeemeDenoiserWeights* w, const float* cond, const float* ttab, const int32_t* trow,
+                                      int trow_per_sample, int n_trow, int Bc, float* ctab, float* catab,
+                                      void* zero, size_t zero_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (Bc <= 0 || n_trow <= 0) return seeme_fail("tables1: empty batch / row list");
+    if (w->ca_fold_w == nullptr) return seeme_fail("tables1: folded key/value weights missing");
+    if (w->ca_pn_w == nullptr || w->ca_po_w == nullptr) return seeme_fail("tables1: proj_out weights missing");
+    if (cond == nullptr || ttab == nullptr || trow == nullptr || ctab == nullptr || catab == nullptr) return seeme_fail("tables1: null table pointer");
+    if (zero_bytes != 0 && (zero == nullptr || ((uintptr_t)zero & 15) != 0)) return seeme_fail("tables1: the zero region must be 16-byte aligned");
+    Tables1Args a{};
+    a.cond = cond; a.ttab = ttab; a.trow = trow; a.per_sample = trow_per_sample; a.n_trow = n_trow;
+    a.R = trow_per_sample ? 1 : n_trow; a.Bc = Bc;
+    const long rows = (long)Bc * a.R;
+    if (rows > (1L << 30) / SEEME_DEN_NL) return seeme_fail("tables1: table too large");
+    a.rows = (int)rows;
+    a.kv_w = w->kv_cat_w; a.kv_b = w->kv_cat_b; a.cf_w = w->ca_fold_w; a.cf_b = w->ca_fold_b; a.ln_w = w->ln_ones; a.ln_b = w->ln_zeros;
+    a.pn_w = w->ca_pn_w; a.pn_b = w->ca_pn_b; a.po_w = w->ca_po_w; a.po_b = w->ca_po_b;
+    a.ctab = ctab; a.catab = catab; a.zero = (unsigned char*)zero; a.zero_bytes = zero_bytes;
+    a.ca_blocks = (a.rows + TILE_M - 1) / TILE_M * SEEME_DEN_NL;
+    a.ct_blocks = (Bc + TILE_M - 1) / TILE_M * 80;
+    const size_t zb = (zero_bytes + 256 * 16 * 4 - 1) / (256 * 16 * 4);   // four 16-byte stores per thread, 64 workgroups at the most
+    a.zero_blocks = (int)(zb < 64 ? zb : 64);
+    const size_t lds = (size_t)2 * TILE_M * T1_LD * sizeof(float);
+    SEEME_HIP(hipFuncSetAttribute((const void*)k_den_tables1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_den_tables1, dim3(a.ca_blocks + a.ct_blocks + a.zero_blocks), dim3(256), lds, st, a);
+    return seeme_check_launch("k_den_tables1");
+}
+
 #ifdef DEN_DBG_TIMES
 extern "C" int seeme_debug_den_times(unsigned long long* host, int n) {
     SEEME_HIP(hipMemcpyFromSymbol(host, HIP_SYMBOL(den_dbg_times), sizeof(unsigned long long) * (size_t)(n < 512 ? n : 512)));

@@ -1232,6 +1232,68 @@ struct ProHArgs {
     float* x;
     const uint4* qkv_w; const float* qkv_b; unsigned short* q_out; uint4* kp_out; uint4* vp_out;
 };
+// Feature rows of frames q0 - 2 .. q0 + 29 as fp16 into R1[32][Kp + HPAD], zero padded to Kp = 32 NB columns.  Every load of a
+// thread is issued before its first conversion, and no index needs a division:
+//   VEC (F % 4 == 0, 16-byte aligned base): thread -> row tid / 8, 16-byte slots (tid % 8) + 8 j, j < NB;
+//   else                                  : thread -> column (tid % 32) + 32 j of rows (tid / 32) + 8 i, i < 4.
+// The guard is a select on the ADDRESS only: bounds-checked buffer loads over the sample's T x F floats, a guarded-out element reads
+// at the end of the record and comes back 0 (see bias_load).  With a select on the value as well, hipcc turns each guard into a
+// branch around its load and waits vmcnt(0) behind every one of them -- the serial round trips this staging is there to avoid.
+template <int NB, bool VEC>
+__device__ __forceinline__ void pro_stage_features(const ProHArgs& a, unsigned short* __restrict__ R1, int lda_h, int b, int q0, int tid) {
+    const unsigned bytes = (unsigned)a.T * (unsigned)a.F * 4u;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.features + (size_t)b * a.T * a.F), 0, (int)bytes, 0x00020000);
+    if (VEC) {
+        const int row = tid >> 3, sl = tid & 7, s = q0 + row;
+        const bool rok = s >= 2 && s < a.S;
+        const unsigned ro = (unsigned)(s - 2) * (unsigned)a.F * 4u;
+        float4 v[NB];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            const int c = 4 * (sl + 8 * j);
+            const bool ok = rok && (j < NB - 1 || c < a.F);      // only the last 32 columns reach past F
+            v[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? ro + 4u * c : bytes, 0, 0));
+        }
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            const unsigned lo = (unsigned)f2h(v[j].x) | ((unsigned)f2h(v[j].y) << 16), hi = (unsigned)f2h(v[j].z) | ((unsigned)f2h(v[j].w) << 16);
+            *reinterpret_cast<uint2*>(R1 + row * lda_h + 4 * (sl + 8 * j)) = make_uint2(lo, hi);
+        }
+    } else {
+        const int cl = tid & 31, rg = tid >> 5;
+        float v[4][NB];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int s = q0 + rg + 8 * i;
+            const bool rok = s >= 2 && s < a.S;
+            const unsigned ro = (unsigned)(s - 2) * (unsigned)a.F * 4u;
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+                const int c = cl + 32 * j;
+                const bool ok = rok && (j < NB - 1 || c < a.F);
+                v[i][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, ok ? ro + 4u * c : bytes, 0, 0));
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < NB; ++j) R1[(rg + 8 * i) * lda_h + cl + 32 * j] = f2h(v[i][j]);
+    }
+}
+template <bool VEC>
+__device__ __forceinline__ void pro_stage_features_nb(const ProHArgs& a, unsigned short* __restrict__ R1, int Kp, int b, int q0, int tid) {
+    const int lda_h = Kp + HPAD;
+    switch (Kp >> 5) {
+        case 1: pro_stage_features<1, VEC>(a, R1, lda_h, b, q0, tid); break;
+        case 2: pro_stage_features<2, VEC>(a, R1, lda_h, b, q0, tid); break;
+        case 3: pro_stage_features<3, VEC>(a, R1, lda_h, b, q0, tid); break;
+        case 4: pro_stage_features<4, VEC>(a, R1, lda_h, b, q0, tid); break;
+        case 5: pro_stage_features<5, VEC>(a, R1, lda_h, b, q0, tid); break;
+        case 6: pro_stage_features<6, VEC>(a, R1, lda_h, b, q0, tid); break;
+        case 7: pro_stage_features<7, VEC>(a, R1, lda_h, b, q0, tid); break;
+        default: pro_stage_features<8, VEC>(a, R1, lda_h, b, q0, tid); break;
+    }
+}
 __global__ __launch_bounds__(256) void k_vae_pro_h(const ProHArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -1244,12 +1306,9 @@ __global__ __launch_bounds__(256) void k_vae_pro_h(const ProHArgs a) {
     if (a.mode == 1) {
         const int Kp = (a.F + 31) & ~31, lda_h = Kp + HPAD;
         const BiasRegs<4> bias = bias_load<4>(a.emb_b, wave * 64, 256);
-        for (int idx = tid; idx < TILE_M * Kp; idx += 256) {       // features of frame s - 2 (guard: select on address and value)
-            const int row = idx / Kp, c = idx - row * Kp, s = q0 + row;
-            const bool ok = s >= 2 && s < a.S && c < a.F;
-            float v = a.features[ok ? ((size_t)b * a.T + (s - 2)) * a.F + c : 0];
-            R1[row * lda_h + c] = f2h(ok ? v : 0.f);
-        }
+        // features of frame s - 2: float4 loads when the rows are 16-byte aligned (checked here, as k_linear's a_vec does)
+        if ((a.F & 3) == 0 && (reinterpret_cast<size_t>(a.features) & 15) == 0) pro_stage_features_nb<true>(a, R1, Kp, b, q0, tid);
+        else pro_stage_features_nb<false>(a, R1, Kp, b, q0, tid);
         __syncthreads();
         f32x4 acc[2][4];
         acc_zero(acc);

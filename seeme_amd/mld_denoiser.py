@@ -181,6 +181,7 @@ class MldDenoiser(nn.Module):
         self.cluster_placement = 1
         self.cluster_flags = 0           # bit 0: write-through granule stores always
         self.cluster_ms = True           # batches above 32: clusters that own up to 8 samples (k_den_cluster_ms)
+        self.fused_tables = True         # sample_loop, one condition token: ctab and catab from one launch (seeme_denoiser_tables1); SEEME_DEN_TABLES=0 turns it off
         self.pack_xcds = "auto"          # one-CU-per-sample launches: XCDs the working workgroups sit on (_lib.default_xcds); 8 = dealt out
 
         d = self.latent_dim
@@ -462,24 +463,57 @@ class MldDenoiser(nn.Module):
                trow.numel(), Bc, catab.data_ptr(), ws.data_ptr(), ws.numel() * 4, L.current_stream())
         return catab
 
-    def _launch(self, latents2d, ctab, ttab, trow, per_sample, steps, sched, coef, noise, cfg, guidance):
-        B, N = latents2d.shape[0], ctab.shape[1]
+    def _fused_tables(self) -> int:
+        """0: cond_tables + ca_tables; 1: one launch (tables1) that also zeroes the exchange buffer; 2 (measurement): one launch, the
+        cluster call zeroes its buffer itself.  SEEME_DEN_TABLES overrides the attribute."""
+        e = os.environ.get("SEEME_DEN_TABLES")
+        return int(self.fused_tables) if e is None else int(e)
+
+    def tables1(self, cond_bf: torch.Tensor, ttab: torch.Tensor, trow: torch.Tensor, per_sample: bool, zero: Optional[torch.Tensor] = None,
+                zero_bytes: int = 0):
+        """ONE condition token: cond_tables + ca_tables as one launch, (ctab [Bc,1,5120], catab [Bc,R,5,256]), the same bits.
+        `zero` (uint8): its first zero_bytes bytes are set to zero by the same launch."""
+        L.require_cuda(cond_bf, "condition")
+        cond_bf = cond_bf.contiguous()
+        Bc, N, _ = cond_bf.shape
+        if N != 1:
+            raise ValueError("tables1: one condition token")
+        R = 1 if per_sample else trow.numel()
+        ctab = torch.empty(Bc, 1, L.CROW, device=cond_bf.device, dtype=torch.float32)
+        catab = torch.empty(Bc, R, 5, self.latent_dim, device=cond_bf.device, dtype=torch.float32)
+        w = self._weights()
+        L.call("seeme_denoiser_tables1", C.byref(w), cond_bf.data_ptr(), ttab.data_ptr(), trow.data_ptr(), int(per_sample), trow.numel(), Bc,
+               ctab.data_ptr(), catab.data_ptr(), L.ptr(zero), int(zero_bytes) if zero is not None else 0, L.current_stream())
+        return ctab, catab
+
+    def _launch(self, latents2d, ctab, ttab, trow, per_sample, steps, sched, coef, noise, cfg, guidance, cond_bf=None):
+        """`ctab` None: one condition token `cond_bf` whose tables this call builds itself, in one launch (tables1)."""
+        fused = ctab is None
+        B, N = latents2d.shape[0], (1 if fused else ctab.shape[1])
         out = torch.empty(B, self.latent_dim, device=latents2d.device, dtype=torch.float32)
+        Cc, spc = self._cluster_plan(B, N, bool(cfg), bool(per_sample), _device_cus(latents2d.device))
+        need = 0
+        if Cc:
+            need = (L.lib().seeme_den_cluster_ms_xchg_bytes(B, Cc, spc) if spc > 1 else L.lib().seeme_den_cluster_xchg_bytes(B, Cc))
+            if self._xchg is None or self._xchg.numel() < need or self._xchg.device != latents2d.device:
+                self._xchg = torch.zeros(need, dtype=torch.uint8, device=latents2d.device)
+        catab = None
+        zeroed = fused and Cc and self._fused_tables() == 1
+        if fused:       # the table launch also zeroes the exchange buffer of the cluster launch that follows it on this stream
+            ctab, catab = self.tables1(cond_bf, ttab, trow, per_sample, self._xchg if zeroed else None, need)
         a = L.SampleArgs()
         a.B, a.N, a.steps, a.sched, a.cfg, a.guidance_scale = B, N, steps, sched, int(cfg), float(guidance)
         a.latents, a.ctab, a.ttab, a.trow, a.trow_per_sample = latents2d.data_ptr(), ctab.data_ptr(), ttab.data_ptr(), trow.data_ptr(), int(per_sample)
         a.coef, a.noise, a.out = L.ptr(coef), L.ptr(noise), out.data_ptr()
-        catab = self.ca_tables(ctab, ttab, trow, per_sample) if N == 1 else None
+        if not fused and N == 1:
+            catab = self.ca_tables(ctab, ttab, trow, per_sample)
         a.catab = L.ptr(catab)
         a.xcds = L.default_xcds((B + 1) // 2 if (B > 256 and not per_sample and not cfg) else B, self.pack_xcds)
         w = self._weights()
-        Cc, spc = self._cluster_plan(B, N, bool(cfg), bool(per_sample), _device_cus(latents2d.device))
         if Cc:
             img, vpc, code = self._cluster_weights(Cc, N > 1)
-            need = (L.lib().seeme_den_cluster_ms_xchg_bytes(B, Cc, spc) if spc > 1 else L.lib().seeme_den_cluster_xchg_bytes(B, Cc))
-            if self._xchg is None or self._xchg.numel() < need or self._xchg.device != latents2d.device:
-                self._xchg = torch.zeros(need, dtype=torch.uint8, device=latents2d.device)
             cl = L.DenCluster()
+            cl.xchg_zeroed = int(bool(zeroed))
             cl.wgc, cl.wdtype, cl.vpc, cl.C = img.data_ptr(), code, vpc.data_ptr(), Cc
             cl.placement = int(os.environ.get("SEEME_DEN_CLUSTER_PLACE", self.cluster_placement))
             cl.flags = int(os.environ.get("SEEME_DEN_CLUSTER_FLAGS", self.cluster_flags))
@@ -537,7 +571,8 @@ class MldDenoiser(nn.Module):
             cached = (tfeat, coef, trow, self.time_tables(tfeat))
             self._table_cache = {key: cached}
         tfeat, coef, trow, ttab = cached
-        ctab = self.cond_tables(cond_bf)
+        fused = cond_bf.shape[1] == 1 and self._fused_tables() != 0    # one condition token: the tables are built inside _launch
+        ctab = None if fused else self.cond_tables(cond_bf)
         steps = len(trow)
         noise = None
         if scheduler.needs_noise(eta):
@@ -548,7 +583,7 @@ class MldDenoiser(nn.Module):
         lat2 = latents.reshape(B, -1).contiguous()
         if events is not None:     # (start, end) torch.cuda.Event pair bracketing only the persistent kernel
             events[0].record()
-        out = self._launch(lat2, ctab, ttab, trow, False, steps, sched, coef, noise, cfg, guidance_scale)
+        out = self._launch(lat2, ctab, ttab, trow, False, steps, sched, coef, noise, cfg, guidance_scale, cond_bf=cond_bf)
         if events is not None:
             events[1].record()
         return out.reshape(1, B, self.latent_dim)
