@@ -849,7 +849,7 @@ def test_ego_eval_variants(dev):
     assert rs2["m_rst"].shape[1] == 12 and rs2["lengths"] == [12, 12] and torch.isfinite(rs2["joints_rst"]).all()
 
 
-@pytest.mark.parametrize("N", [1, 2])
+@pytest.mark.parametrize("N", [1, 2, 3, 4])
 def test_hip_backward_matches_autograd(dev, N):
     """Hand-written backward of the denoiser chain (k_den_bwd + host batch reductions) vs PyTorch autograd over the
     differentiable twin: loss, every parameter gradient and the gradient of the condition tokens."""
