@@ -687,6 +687,39 @@ enum { SEEME_STITCH_ANGLE = 0, SEEME_STITCH_ANGLE_TRANSL = 1, SEEME_STITCH_ROT6D
 #define SEEME_STITCH_NLERP_DOT 0.9995f
 int seeme_stitch_windows(const float* feats, int W, int T, int O, int n_frames, int F, int layout, float* out, void* stream);
 
+/* ------------------------------------------------------------------ one coherent track through sparse key frames (csrc/track.hip)
+ * Lf key frames (the stored frames of a recording of L frames, idx [Lf] int32 on the device, strictly increasing inside 0..L-1: the
+ * caller's contract) carry S candidate bodies each.  ONE candidate per key frame is chosen by seeme_path_select (W = Lf, K = S) with the
+ * transition costs below, and the chosen bodies are filled to all L frames and filtered.  fp32, no atomics: bitwise reproducible.
+ *
+ * Transition costs of a random walk of every joint whose variance grows linearly over a gap.  jts [Lf,S,24,3] fp32 metres (16-byte
+ * aligned): cost[l,i,j] = weight * (sum over the 24 joints, in joint order, of |jts[l,i,k] - jts[l+1,j,k]|^2) / (idx[l+1] - idx[l]),
+ * cost [Lf-1,S,S].  weight = 1e6 / (2 step_mm^2) makes it the negative log-density (nats, without the constant) of a walk with a
+ * standard deviation of step_mm per frame.  1 <= S <= 32, 1 <= Lf <= 65536; Lf = 1 writes nothing and succeeds.  One workgroup per l,
+ * fixed summation order. */
+int seeme_track_cost(const float* jts, const int32_t* idx, int Lf, int S, float weight, float* cost, void* stream);
+
+/* Fill between the keys and a symmetric FIR.  pose [Lf,J,3] axis-angle at the key frames idx [Lf] (device), transl [Lf,3] or NULL;
+ * taps_host [R+1] on the HOST, 0 <= R <= 32, taps[0] > 0, every tap finite and >= 0 (validated; they reach the kernel by value).
+ * pose_out [L,J,3], transl_out [L,3] or NULL (with transl: both or neither).  1 <= J <= 32, 1 <= Lf <= L <= 2^20.
+ * A unit is one joint rotation or the translation.  The quaternion of a key is the one seeme_stitch_windows forms from an axis-angle
+ * vector v: (cos(|v|/2), sin(|v|/2) v/|v|).
+ * fill(m) for a recording frame m: the first key for m <= idx[0]; the last key for m >= idx[Lf-1]; key a itself when m == idx[a];
+ *   otherwise, with idx[a] < m < idx[a+1] and u = (m - idx[a]) / (idx[a+1] - idx[a]), exactly seeme_stitch_windows' blend of keys a
+ *   and a+1 at u (the later key negated on a negative dot product, then the slerp, or the lerp above SEEME_STITCH_NLERP_DOT,
+ *   normalised).  The translation: a + u (b - a).
+ * out(n): over the window m = max(0, n-R) .. min(L-1, n+R), acc = sum_m taps[|m-n|] * s_m * fill(m) with s_m = -1 when
+ *   dot(fill(m), fill(n)) < 0 and +1 otherwise, summed in increasing m; the rotation is acc / |acc| (acc . fill(n) >= taps[0] > 0: it
+ *   never vanishes), written as axis-angle with an angle in [0, pi] as the stitch kernel writes it.  The translation is
+ *   sum_m taps[|m-n|] * fill_t(m) / sum_m taps[|m-n|] over the same truncated window.
+ * With R == 0 a frame that is a key is copied from the input bit for bit (no round trip through the quaternion); with R > 0 nothing is
+ * copied.  One launch: a workgroup owns SEEME_TRACK_TILE output frames, finds the key interval of each of its TILE + 2R frames by
+ * binary search, holds their fill in LDS and applies the taps from there.  The result depends neither on the tiling nor on what the
+ * outputs held before. */
+#define SEEME_TRACK_TILE 64
+int seeme_track_filter(const float* pose, const float* transl, const int32_t* idx, int Lf, int L, int J,
+                       const float* taps_host, int R, float* pose_out, float* transl_out, void* stream);
+
 /* ------------------------------------------------------------------ scene views of a moving camera (csrc/scene_views.hip)
  * The view-dependent selection of a scene mesh's vertices that the EgoBody scene tables are made with (EgoHMR
  * preprocess_scene_s1.py:91-114: into the camera frame, keep z > 0, every k-th survivor, the first P), for W views in one call.

@@ -562,7 +562,9 @@ def load_proscene(model, state: Dict, path: str) -> str:
 def estimate_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=None) -> Dict:
     """estimate.py: a recording .npz WITHOUT the interactee (video or image_crops, center, scale, cam_intrinsics, world2cam,
     scene_vertices) -> the same recording with the interactee's global_orient, body_pose, transl and betas as the
-    ProHMR-scene head estimates them, in the recording's world frame: a file predict.py accepts."""
+    ProHMR-scene head estimates them, in the recording's world frame: a file predict.py accepts.  --track: the head runs at the
+    stored frames only (video_index may skip frames) and the output's motion is ONE track through its samples, filled to every
+    recording frame and smoothed (seeme_amd/track.py)."""
     import numpy as np
     from . import crops as CR
     from . import geometry as G
@@ -578,10 +580,20 @@ def estimate_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=
     g.add_argument("--seed", type=int, default=None, help="seed of the draws (default: SEED_VALUE)")
     g.add_argument("--save_samples", action="store_true", help="also store interactee_samples_{global_orient,body_pose,transl} [L,S,...]")
     g.add_argument("--chunk_frames", type=int, default=64, help="frames per pass: bounds the scene clouds (scene_points x 12 bytes each)")
+    t = p.add_argument_group("one coherent track (seeme_amd/track.py, INTEGRATION.md N)")
+    t.add_argument("--track", action="store_true", help="estimate at the STORED frames only (video_index may skip frames), choose one "
+                   "sample per stored frame by the min-sum path, fill every recording frame between them and smooth the result")
+    t.add_argument("--track_sigma", type=float, default=None, help="override TEST.TRACK_SIGMA: Gaussian width of the filter, frames (0..10)")
+    t.add_argument("--track_step_mm", type=float, default=None, help="override TEST.TRACK_STEP_MM: the random walk's step, mm per frame")
+    t.add_argument("--track_prior_weight", type=float, default=None,
+                   help="override TEST.TRACK_PRIOR_WEIGHT: weight of the flow's log-density against the transitions")
     p.set_defaults(scene_points=None, frames=16)
     args = p.parse_args(argv)
     cfg = load_cfg(args, "test")
     cfg.model.interactee_head = True
+    for key, v in (("TRACK_SIGMA", args.track_sigma), ("TRACK_STEP_MM", args.track_step_mm), ("TRACK_PRIOR_WEIGHT", args.track_prior_weight)):
+        if v is not None:
+            cfg.TEST[key] = v
     if args.scene_points is not None:
         cfg.TEST.SCENE_VIEW_POINTS = args.scene_points
     args.scene_points = P = int(cfg.TEST.get("SCENE_VIEW_POINTS", 20000))
@@ -604,38 +616,41 @@ def estimate_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=
     ck = read_checkpoint(ckpt)
     log.info("Loading the %s modules of %s", load_proscene(model, ck.get("state_dict", ck), ckpt), ckpt)
     model = model.to(dev).eval()
-    rec = R.load_recording(args.input, video=args.video, require_interactee=False)
+    rec = R.load_recording(args.input, video=args.video, require_interactee=False, allow_sparse=args.track)
     n = int(rec["n_frames"])
+    vi = np.asarray(rec["video_index"], np.int64)                       # the recording frame of every stored frame: 0..L-1 without --track
+    nf = int(vi.shape[0])
     view = R.opencv_views(rec["world2cam"], model.interactee_camera_axes)               # [L,4,4] float64: world -> OpenCV camera
     verts = torch.from_numpy(np.ascontiguousarray(rec["scene_vertices"], np.float32)).to(dev)
     gen = torch.Generator().manual_seed(int(cfg.SEED_VALUE) if args.seed is None else args.seed)
-    z = PH.draw_z(n, S, gen)                                            # drawn for the whole recording: chunking changes nothing
+    z = PH.draw_z(nf, S, gen)                                           # drawn for the whole recording: chunking changes nothing
     got = {k: [] for k in ("rotmat", "betas", "cam", "log_prob", "transl", "count")}
     with torch.no_grad():
-        for lo in range(0, n, args.chunk_frames):
-            hi = min(n, lo + args.chunk_frames)
-            c, s_ = rec["center"][lo:hi], rec["scale"][lo:hi]
+        for lo in range(0, nf, args.chunk_frames):                      # rows lo..hi-1 of the stored frames
+            hi = min(nf, lo + args.chunk_frames)
+            fr = vi[lo:hi]
+            c, s_ = rec["center"][fr], rec["scale"][fr]
             if "video" in rec:
                 frames = torch.from_numpy(np.ascontiguousarray(rec["video"][lo:hi])).to(dev)
                 patches = CR.crop_patches_hip(frames, np.arange(hi - lo), PH.head_box(c, s_))
             else:
                 patches = torch.from_numpy(np.ascontiguousarray(rec["image_crops"][lo:hi])).to(dev)
-            sv = R.scene_views_hip(verts, torch.from_numpy(view[lo:hi]).float().to(dev), P)
+            sv = R.scene_views_hip(verts, torch.from_numpy(view[fr]).float().to(dev), P)
             count = sv["count"].cpu()
             if bool((count == 0).any()):
-                f = lo + int(torch.nonzero(count == 0)[0])
+                f = int(fr[int(torch.nonzero(count == 0)[0])])
                 raise ValueError(f"{args.input}: frame {f} sees no scene vertex (scene_view_count 0): its camera pose looks away from "
                                  "scene_vertices (is TEST.INTERACTEE_CAMERA_AXES right for this world2cam?)")
-            out = model.estimate_interactee(patches, sv["cloud"], c, s_, rec["cam_intrinsics"][lo:hi], z=z[lo:hi])
+            out = model.estimate_interactee(patches, sv["cloud"], c, s_, rec["cam_intrinsics"][fr], z=z[lo:hi])
             for k in ("rotmat", "betas", "cam", "log_prob", "transl"):
                 got[k].append(out[k])
             got["count"].append(count)
     cat = {k: torch.cat(v) for k, v in got.items()}
-    aa = G.rotmat_to_aa_torch(cat["rotmat"].double()).reshape(n, S, 72)                 # camera frame, every sample
+    aa = G.rotmat_to_aa_torch(cat["rotmat"].double()).reshape(nf, S, 72)                # camera frame, every sample
     betas = cat["betas"].double().mean(dim=0)
     # to the world; SMPL turns about the rest pelvis of the betas the body is posed with: the file's betas, the mean
     J0 = R.rest_pelvis(model.smpl_model, betas[None].to(dev))[0].double()
-    go, tr = R.camera_body_to_world(aa[:, :, :3], cat["transl"].double()[:, None].expand(n, S, 3), J0, rec["world2cam"],
+    go, tr = R.camera_body_to_world(aa[:, :, :3], cat["transl"].double()[:, None].expand(nf, S, 3), J0, rec["world2cam"][vi],
                                     model.interactee_camera_axes)
     f32 = lambda t: t.float().cpu().numpy()
     with np.load(args.input, allow_pickle=False) as zf:
@@ -646,12 +661,26 @@ def estimate_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=
     if args.save_samples:
         res.update(interactee_samples_global_orient=f32(go), interactee_samples_body_pose=f32(aa[:, :, 3:]),
                    interactee_samples_transl=f32(tr))
+    trk = None
+    if args.track:                                                      # one sample per stored frame, every recording frame filled
+        from . import track as TK
+        trk = TK.track_interactee(go, aa[:, :, 3:], tr[:, 0], cat["log_prob"], vi, n, model.smpl_model, betas.to(dev),
+                                  step_mm=model.track_step_mm, prior_weight=model.track_prior_weight, sigma=model.track_sigma, device=dev)
+        res.update(interactee_raw_global_orient=res["global_orient"], interactee_raw_body_pose=res["body_pose"],
+                   interactee_raw_transl=res["transl"], interactee_frames=vi, interactee_path=trk["path"].cpu().numpy(),
+                   interactee_step_cost=f32(trk["step_cost"]))
+        res.update(global_orient=f32(trk["global_orient"]), body_pose=f32(trk["body_pose"]), transl=f32(trk["transl"]))
     d = os.path.dirname(os.path.abspath(args.output))
     os.makedirs(d, exist_ok=True)
     with open(args.output, "wb") as f:
         np.savez(f, **res)
     log.info("%d frames, %d samples each; mean log-probability of the mode %.2f; written to %s", n, S,
              float(cat["log_prob"][:, 0].mean()), args.output)
+    if trk is not None:
+        log.info("track through %d stored frames: path cost %.2f nats, mean step cost %.2f", nf, float(trk["path_cost"]),
+                 float(trk["step_cost"].mean()) if nf > 1 else 0.0)
+        return {"file": args.output, "n_frames": n, "num_samples": S, "stored_frames": nf, "path": trk["path"].tolist(),
+                "path_cost": float(trk["path_cost"])}
     return {"file": args.output, "n_frames": n, "num_samples": S}
 
 

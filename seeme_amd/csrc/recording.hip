@@ -3,6 +3,7 @@
 // (seeme_path_select) and the stitched motion of that path (seeme_stitch_windows).  Definitions: include/seeme_hip.h; the plain-torch
 // twins are in seeme_amd/recording.py.  fp32 throughout, no atomics: every result is bitwise reproducible.
 #include "api_util.hpp"
+#include "rec_quat.hpp"
 #include <stdint.h>
 
 #define REC_KMAX 32
@@ -215,26 +216,7 @@ extern "C" int seeme_path_select(const float* cost, const float* unary, int W, i
 // One lane per (frame n of the recording, unit): a unit is one joint rotation (3 axis-angle or 6 rot6d values) or the translation.
 // Frame n belongs to window w = min(n / S, W-1), S = T - O, at local frame t = n - w*S; when w >= 1 and t < O it is also frame t + S
 // of window w-1 and the two are blended with weight u = (t+1)/(O+1) for window w, otherwise the unit is copied.
-struct RecQuat { float w, x, y, z; };
-
-__device__ __forceinline__ RecQuat rec_normalize(RecQuat q) {
-    const float n = sqrtf(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z);
-    return {q.w / n, q.x / n, q.y / n, q.z / n};
-}
-
-__device__ __forceinline__ RecQuat rec_aa_to_quat(const float* a) {
-    const float th = sqrtf(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-    const float k = th > 1e-6f ? sinf(0.5f * th) / th : 0.5f - th * th / 48.f;
-    return {cosf(0.5f * th), k * a[0], k * a[1], k * a[2]};
-}
-
-__device__ __forceinline__ void rec_quat_to_aa(RecQuat q, float* a) {
-    if (q.w < 0.f) { q.w = -q.w; q.x = -q.x; q.y = -q.y; q.z = -q.z; }           // angle in [0, pi]
-    const float vn = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z);
-    const float k = vn > 1e-12f ? 2.f * atan2f(vn, q.w) / vn : 2.f;
-    a[0] = k * q.x; a[1] = k * q.y; a[2] = k * q.z;
-}
-
+// (RecQuat, rec_normalize, rec_aa_to_quat, rec_quat_to_aa and rec_blend: rec_quat.hpp, shared with track.hip)
 // model-side rot6d (geometry.rot6d_to_rotmat 'prohmr'): a1 = x[0:3], a2 = x[3:6], Gram-Schmidt, columns b1, b2, b1 x b2
 __device__ __forceinline__ RecQuat rec_rot6d_to_quat(const float* x) {
     const float n1 = fmaxf(sqrtf(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]), 1e-12f);
@@ -268,19 +250,6 @@ __device__ __forceinline__ void rec_quat_to_rot6d(RecQuat q, float* x) {        
     const float w = q.w, a = q.x, b = q.y, c = q.z;
     x[0] = 1.f - 2.f * (b * b + c * c); x[1] = 2.f * (a * b + w * c); x[2] = 2.f * (a * c - w * b);
     x[3] = 2.f * (a * b - w * c); x[4] = 1.f - 2.f * (a * a + c * c); x[5] = 2.f * (b * c + w * a);
-}
-
-// the later one flipped onto the earlier one's hemisphere, slerp, normalised lerp above SEEME_STITCH_NLERP_DOT
-__device__ __forceinline__ RecQuat rec_blend(RecQuat p, RecQuat q, float u) {
-    float dt = p.w * q.w + p.x * q.x + p.y * q.y + p.z * q.z;
-    if (dt < 0.f) { dt = -dt; q.w = -q.w; q.x = -q.x; q.y = -q.y; q.z = -q.z; }
-    float kp = 1.f - u, kq = u;
-    if (!(dt > SEEME_STITCH_NLERP_DOT)) {
-        const float th = acosf(dt), s = sinf(th);
-        kp = sinf((1.f - u) * th) / s;
-        kq = sinf(u * th) / s;
-    }
-    return rec_normalize({kp * p.w + kq * q.w, kp * p.x + kq * q.x, kp * p.y + kq * q.y, kp * p.z + kq * q.z});
 }
 
 __global__ __launch_bounds__(REC_THREADS) void k_stitch_windows(const float* __restrict__ feats, int W, int T, int O, int n_frames,

@@ -52,6 +52,7 @@ from .respointnet import ResnetPointnet
 from .shapes import motion_layout
 from .smpl import SMPL
 from .social_metrics import DEFAULT_DIST_EDGES, DEFAULT_GAZE_EDGES, SocialMetrics, check_edges, social_metrics_hip
+from .track import DEFAULT_PRIOR_WEIGHT, DEFAULT_SIGMA, DEFAULT_STEP_MM, check_prior_weight, check_sigma, check_step_mm
 
 
 IMAGE_FEAT_DIM = 2048          # pooled ResNet-50 feature of proscene.encode_image (prohmr_scene.py:99-100, BACKBONE.OUT_CHANNELS)
@@ -390,6 +391,11 @@ class MLD(nn.Module):
         if isinstance(self.path_medoid_weight, bool) or not isinstance(self.path_medoid_weight, (int, float)) \
                 or not 0 <= self.path_medoid_weight < float("inf"):
             raise ValueError(f"TEST.PATH_MEDOID_WEIGHT must be a finite number >= 0, got {self.path_medoid_weight!r}")
+        # estimate.py --track (seeme_amd/track.py): the random walk's step (mm per frame), the weight of the flow's density against the
+        # transitions and the Gaussian width of the filter (frames).  None of the three was tuned on data.
+        self.track_step_mm = check_step_mm(cfg.TEST.get("TRACK_STEP_MM", DEFAULT_STEP_MM), "TEST.TRACK_STEP_MM")
+        self.track_prior_weight = check_prior_weight(cfg.TEST.get("TRACK_PRIOR_WEIGHT", DEFAULT_PRIOR_WEIGHT), "TEST.TRACK_PRIOR_WEIGHT")
+        self.track_sigma = check_sigma(cfg.TEST.get("TRACK_SIGMA", DEFAULT_SIGMA), "TEST.TRACK_SIGMA")
         # PA-MPJPE, V2V and body-scene contact per hypothesis (seeme_amd/mesh_metrics.py): off = today's result, key for key
         self.mesh_metrics = cfg.TEST.get("MESH_METRICS", False)
         if not isinstance(self.mesh_metrics, bool):

@@ -511,9 +511,10 @@ def camera_body_to_world(global_orient, cam_t, J0, world2cam, axes):
 _ESTIMATE_KEYS = ("center", "scale", "cam_intrinsics", "world2cam", "scene_vertices")
 
 
-def _check_estimate_input(rec, n: int, path: str) -> None:
+def _check_estimate_input(rec, n: int, path: str, allow_sparse: bool = False) -> None:
     """What ``estimate`` reads of a recording without interactee keys: the box, the intrinsics, the camera path, the scene's vertices
-    and an image for EVERY recording frame."""
+    and an image for EVERY recording frame (allow_sparse: for the stored frames of video_index only; ``estimate.py --track`` fills the
+    frames between them)."""
     missing = [k for k in _ESTIMATE_KEYS if k not in rec]
     if missing:
         raise ValueError(f"{path}: missing {missing}; estimating the interactee needs {list(_ESTIMATE_KEYS)} and video or image_crops")
@@ -525,13 +526,14 @@ def _check_estimate_input(rec, n: int, path: str) -> None:
             raise ValueError(f"{path}: {k} is {rec[k].shape} {rec[k].dtype}: expected floats {list(shape)} (L = {n})")
         rec[k] = np.asarray(rec[k], np.float32)
     vi = rec["video_index"]
-    if vi.shape[0] != n:                                   # strictly increasing inside 0..L-1: fewer than L entries skip a frame
+    if vi.shape[0] != n and not allow_sparse:              # strictly increasing inside 0..L-1: fewer than L entries skip a frame
         f = int(np.argmax(vi != np.arange(vi.shape[0]))) if (vi != np.arange(vi.shape[0])).any() else int(vi.shape[0])
         raise ValueError(f"{path}: frame {f} has no stored image (video_index skips it): every recording frame needs one; filling "
                          "between sparse estimates is not built")
 
 
-def load_recording(path: str, video: Optional[str] = None, require_interactee: bool = True) -> Dict[str, np.ndarray]:
+def load_recording(path: str, video: Optional[str] = None, require_interactee: bool = True,
+                   allow_sparse: bool = False) -> Dict[str, np.ndarray]:
     """A recording ``.npz`` (read with allow_pickle=False: an object array is refused): the INTERACTEE's global_orient [L,3],
     body_pose [L,69|63], transl [L,3], betas [10]; optionally scene [P,3], image_feats [L,2048], wearer_betas [10].  float32.
     A moving camera adds world2cam [L,4,4], the rigid map from the recording's world frame to every frame's camera frame (float64:
@@ -547,7 +549,9 @@ def load_recording(path: str, video: Optional[str] = None, require_interactee: b
     cam_intrinsics, [3] or [L,3] = (f, cx, cy) in pixels, is validated when present (``check_intrinsics``) and returned as [L,3].
     require_interactee=False reads the INPUT of ``estimate``: a recording WITHOUT the four interactee keys, whose
     length L is that of center [L,2]; it needs center, scale, cam_intrinsics, world2cam, scene_vertices and an image per frame.  A
-    file that holds interactee keys is refused there: it is an input of predict already."""
+    file that holds interactee keys is refused there: it is an input of predict already.  allow_sparse=True (with
+    require_interactee=False) accepts a video_index that skips frames: center / scale / cam_intrinsics / world2cam stay [L,...] and are
+    read at the stored frames (``estimate.py --track``, seeme_amd/track.py)."""
     with np.load(path, allow_pickle=False) as z:
         missing = [k for k in _REC_KEYS if k not in z.files]
         if require_interactee and missing:
@@ -590,7 +594,7 @@ def load_recording(path: str, video: Optional[str] = None, require_interactee: b
     if "world2cam" in rec:
         check_world2cam(rec["world2cam"], n, path)
     if not require_interactee:
-        _check_estimate_input(rec, n, path)
+        _check_estimate_input(rec, n, path, bool(allow_sparse))
     rec["n_frames"] = n
     return rec
 
