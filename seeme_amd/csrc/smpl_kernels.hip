@@ -135,11 +135,13 @@ __global__ __launch_bounds__(256) void k_smpl_joints(const SmplKArgs a) {
             a.feat[(size_t)m * SMPL_FEAT + i] = i < 10 ? beta[i] : (i < 217 ? sPF[wave][i - 10] : 0.f);
     // ---- 21 extra joints = posed vertices picked by id (compact model)
     if (lane < SMPL_EX * 3) {
-        float v = a.m.ex_template[lane];
+        // the 217 blend terms are summed on their own and meet the template once, as in the GEMM of the full mesh (bias last):
+        // accumulated onto the template, each of them would round at the template coordinate's ulp (~1e-6 of the body in all)
+        float v = 0.f;
 #pragma unroll
         for (int l = 0; l < 10; ++l) v = fmaf(a.m.ex_shapedirs[lane * 10 + l], beta[l], v);
         for (int k = 0; k < 207; ++k) v = fmaf(sPF[wave][k], a.m.ex_posedirs[k * 63 + lane], v);
-        sV[wave][lane] = v;
+        sV[wave][lane] = a.m.ex_template[lane] + v;
     }
     __syncthreads();
     if (live && lane < SMPL_EX) {
@@ -337,7 +339,11 @@ __global__ __launch_bounds__(256) void k_smpl_joints_bwd(const SeemeSmplModel m,
         const float e[3] = {aa[0] + 1e-8f, aa[1] + 1e-8f, aa[2] + 1e-8f};
         const float th = sqrtf(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
         const float d[3] = {aa[0] / th, aa[1] / th, aa[2] / th};
-        const float sn = sinf(th), c = cosf(th), c1 = 1.f - c;
+        // 1 - cos(th) as 2 sin^2(th / 2): the factor meets pd ~ 1 / th below, and 1.f - cosf(th) carries an absolute error of
+        // ~3e-8 whatever th is (1e-3 of the gradient at th = 1e-4).  The forward recompute above keeps 1 - cos: there the error
+        // stays absolute.
+        const float sh = sinf(0.5f * th);
+        const float sn = sinf(th), c = cosf(th), c1 = 2.f * sh * sh;
         const float dd = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
         const float tr = g[0] + g[4] + g[8];
         const float w[3] = {g[7] - g[5], g[2] - g[6], g[3] - g[1]};                       // sum(gR o K(v)) = v . w
