@@ -38,6 +38,17 @@ def _device_cus(device) -> int:
     return _CUS[idx]
 
 
+def _coef_key(scheduler) -> tuple:
+    """What, besides timesteps and eta, identifies a scheduler's coef_table(): the scheduler's own coef_key() (seeme_amd.schedulers), and
+    for an object without one its identity plus whatever configuration it shows.  (sample_loop keeps such an object alive next to its
+    cached table, so the id is not handed to another object while the entry exists.)"""
+    f = getattr(scheduler, "coef_key", None)
+    if callable(f):
+        return (type(scheduler).__name__, f())
+    cfg = getattr(scheduler, "config", None)
+    return (type(scheduler).__name__, id(scheduler), repr(sorted(vars(cfg).items())) if hasattr(cfg, "__dict__") else repr(cfg))
+
+
 def timestep_features(timesteps: torch.Tensor, dim: int = 256, flip_sin_to_cos: bool = True,
                       freq_shift: float = 0.0, max_period: int = 10000) -> torch.Tensor:
     """Sinusoidal timestep features, tools/embeddings.py:245-285 (host-side plumbing: a [rows,256]
@@ -193,6 +204,7 @@ class MldDenoiser(nn.Module):
         self._wcache = None
         self._ws = L.Workspace(per_stream=False)
         self._table_cache = {}
+        self._coef_cache = {}
         self._ccache = {}
         self._xchg = None
 
@@ -558,19 +570,26 @@ class MldDenoiser(nn.Module):
         if cond_bf.shape[0] != (2 * B if cfg else B):
             raise ValueError("condition batch must be B (or 2B with classifier-free guidance)")
         dev = latents.device
-        key = (tuple(scheduler.timesteps.tolist()), float(eta), type(scheduler).__name__)
+        key = tuple(scheduler.timesteps.tolist())
         self._weights()                      # first: a changed parameter drops the time tables cached for the old weights
         cached = self._table_cache.get(key)
         if cached is None:
             tfeat = timestep_features(scheduler.timesteps.cpu(), self.text_encoded_dim, self.flip_sin_to_cos,
                                       self.freq_shift).to(dev)
-            coef = scheduler.coef_table(eta).to(dev)
             trow = torch.arange(len(scheduler.timesteps), dtype=torch.int32, device=dev)
             # the time tables are a function of (weights, timestep schedule) only -- like the packed weight image
-            # they are built once per scheduler configuration (_weights() drops the cache when a parameter changes)
-            cached = (tfeat, coef, trow, self.time_tables(tfeat))
+            # they are built once per timestep schedule (_weights() drops the cache when a parameter changes)
+            cached = (tfeat, trow, self.time_tables(tfeat))
             self._table_cache = {key: cached}
-        tfeat, coef, trow, ttab = cached
+        tfeat, trow, ttab = cached
+        # the coefficient table is a function of everything coef_table() reads: the timesteps, eta and the scheduler's configuration
+        # (clip_sample, prediction_type, the beta schedule ...), so two schedulers with the same timesteps do not share one
+        ckey = (key, float(eta), str(dev), _coef_key(scheduler))
+        centry = self._coef_cache.get(ckey)
+        if centry is None:
+            centry = (scheduler.coef_table(eta).to(dev), scheduler)
+            self._coef_cache = {ckey: centry}
+        coef = centry[0]
         fused = cond_bf.shape[1] == 1 and self._fused_tables() != 0    # one condition token: the tables are built inside _launch
         ctab = None if fused else self.cond_tables(cond_bf)
         steps = len(trow)

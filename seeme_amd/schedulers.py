@@ -72,6 +72,12 @@ class _SchedulerBase:
     def _acp_np(self):
         return self.alphas_cumprod.numpy()
 
+    def coef_key(self) -> tuple:
+        """Everything coef_table() reads besides ``timesteps`` and ``eta``: what a cached table has to be keyed on."""
+        c = self.config
+        return (type(self).__name__, c.num_train_timesteps, c.beta_start, c.beta_end, c.beta_schedule, bool(c.clip_sample),
+                c.prediction_type, self.num_inference_steps)
+
 
 class DDIMScheduler(_SchedulerBase):
     """configs/modules/scheduler.yaml:1-14."""
@@ -90,6 +96,9 @@ class DDIMScheduler(_SchedulerBase):
         self.timesteps = torch.from_numpy(ts)
         if device is not None:
             self.timesteps = self.timesteps.to(device)
+
+    def coef_key(self) -> tuple:
+        return super().coef_key() + (bool(self.config.set_alpha_to_one),)
 
     def _alphas(self, t: int):
         prev_t = t - self.config.num_train_timesteps // self.num_inference_steps
