@@ -488,7 +488,8 @@ def test_vae_hip_backward_matches_autograd(dev, cfg_name, B, T):
     GEMMs, LayerNorm / softmax / GELU backward kernels, weight gradients as split atomic reductions) against the same step on
     the PyTorch-autograd twin (TRAIN.HIP_VAE_BACKWARD false; pinned to the HIP forward and the oracle above): loss terms,
     m_rst, and EVERY parameter gradient, with ragged lengths; T = 70 crosses a 64-row tile edge; B = 64 makes the row counts
-    multiples of 128, so the projections run on the specialised seeme_gemm128 kernel (both forms)."""
+    multiples of 128, so the projections run on the specialised seeme_gemm128 kernel (both forms).  Per sample, per part and
+    against float64, with the tile edges and the plan life cycle: tests/test_gpu_vae_train.py."""
     got = []
     for hip in (True, False):
         def mut(cfg):
@@ -524,7 +525,7 @@ def test_vae_hip_training_dropout_matches_twin_with_same_masks(dev):
     """Training mode: vae_train.py applies the reference's dropout sites (attention weights, dropout1/2/3, the FFN's inner
     dropout, the dropped-out single-key cross-attention weight; cross_attention.py:264-273,324-337) with keep-masks it draws
     itself.  With those very masks injected into the autograd twin, outputs and every parameter gradient agree; the masks keep
-    ~90 % of the elements; eval mode draws none."""
+    ~90 % of the elements; eval mode draws none.  (Per sample against the float64 twin, at three shapes: tests/test_gpu_vae_train.py.)"""
     from seeme_amd.vae_train import VaeTrainer
     from seeme_amd.vae_autograd import vae_encode_torch, vae_decode_torch
     from test_gpu_parity import make_vae
