@@ -218,7 +218,7 @@ typedef struct {
     const float* ttab;     /* [rows, SEEME_TROW] */
     const int32_t* trow;   /* sampling: [steps] row of ttab per step; forward: [B] row per sample */
     int trow_per_sample;   /* 0: trow[step], 1: trow[b] */
-    const float* coef;     /* [steps,8] scheduler scalars per step (see seeme_amd/schedulers.py) */
+    const float* coef;     /* [steps,8] scheduler scalars per step (see seeme_amd/schedulers.py); required unless sched == SEEME_SCHED_NONE */
     const float* noise;    /* optional [steps,B,256] step noise (eta>0 / DDPM), NULL otherwise */
     float* out;            /* [B,256] */
     const float* catab;    /* N == 1: [B or 2B, R, 5, 256] from seeme_denoiser_ca_tables (R = steps, or 1 with trow_per_sample) */

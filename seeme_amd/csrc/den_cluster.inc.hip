@@ -442,7 +442,7 @@ struct ClRowG {
         const int j = wave - 1 - (wave > 5 ? 5 : 0);
         const float* src = (j < 2 ? tt_row + l * 512 + j * 256 : (j < 4 ? tt_row + 2560 + l * 1024 + 512 + (j - 2) * 256 : ca_row)) + 4 * lane;
         if (wave == 6 && A.sched != SEEME_SCHED_NONE) src = A.coef + (size_t)step * 8 + 4 * (lane & 1);
-        if (wave == 7 && A.noise != nullptr) src = A.noise + ((size_t)step * A.B + b) * 256 + 4 * lane;
+        if (wave == 7 && A.noise != nullptr) src = sched_noise_row(A.noise, A.B, step, b, lane);
         r = *reinterpret_cast<const float4*>(src);
     }
     // one LDS write per wave: rows 0 .. 4 (waves 1 .. 5) | COEF (wave 6: every lane pair writes the same 8 floats) | NZ (wave 7); returns the next step's row
@@ -452,22 +452,6 @@ struct ClRowG {
         return __builtin_amdgcn_readfirstlane(t);
     }
 };
-
-// One element of scheduler.step as the loop below forms it when the compiler contracts it with the coefficients in scalar-load pairs (c2 | c3,
-// c4 | c5): elements 0 .. 2 of a lane are one chain of fused multiply-adds, element 3 is paired differently -- fma(c2, x0, c3 ep), an unfused
-// c5 x added, then fma(c4, n, .) -- in every kernel of this file and in k_den_cluster_ms.  With the coefficients read from LDS the compiler no
-// longer sees those pairs and would chain element 3 like the others (one ulp in every fourth latent), so the two-wave-group kernels spell
-// the sums out: the same bits as before, and as the eight-wave body they are tested against.  Both divisions are divisions.
-__device__ __forceinline__ float cl_sched_elem(bool e3, float x, float e, float n, float c0, float c1, float c2, float c3, float c4, float c5,
-                                               float clip, float ptype) {
-#pragma clang fp contract(off)
-    float x0, ep;
-    if (ptype == 0.f) { ep = e; x0 = fmaf(-c1, ep, x) / c0; }
-    else              { x0 = e; ep = fmaf(-c0, x0, x) / c1; }
-    if (clip != 0.f) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-    if (e3) return fmaf(c4, n, c5 * x + fmaf(c2, x0, c3 * ep));
-    return fmaf(c4, n, fmaf(c5, x, fmaf(c3, ep, c2 * x0)));
-}
 
 template <int C, bool Q>
 struct ClStage {
@@ -573,9 +557,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
     if (epi) __builtin_amdgcn_s_setprio(3);
 
     typedef const __attribute__((address_space(4))) int32_t* CI32;
-    typedef const __attribute__((address_space(4))) float* CF32;
     const CI32 trow_c = (CI32)(uintptr_t)A.trow;
-    const CF32 coef_c = (CF32)(uintptr_t)A.coef;
     int row = A.trow_per_sample ? trow_c[b] : trow_c[0];
 
     // ---- prologue: constants, small operands (resident: all layers; Q: layer 0), zeroed fragment buffers, first input, first RU units, the XCC census
@@ -1231,35 +1213,11 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster(const ClArgs ka) {
                     if (A.sched == SEEME_SCHED_NONE) {
                         st4(KEEP + 4 * lane, e);
                     } else {
-                        float c0, c1, c2, c3, c4, c5, clip, ptype;
+                        // two wave groups: coefficients and noise row are in LDS since this step's X1 windows (ClRowG)
+                        const SchedCoef k = GRP ? sched_coef_lds(COEF) : sched_coef_row(A.coef, step);
                         float4 nz = make_float4(0.f, 0.f, 0.f, 0.f);
-                        if constexpr (GRP) {      // in LDS since this step's X1 windows (ClRowG); uniform values back into scalar registers
-                            const float4 k0 = ld4(COEF), k1 = ld4(COEF + 4);
-                            const auto sc = [](float v) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v))); };
-                            c0 = sc(k0.x); c1 = sc(k0.y); c2 = sc(k0.z); c3 = sc(k0.w); c4 = sc(k1.x); c5 = sc(k1.y); clip = sc(k1.z); ptype = sc(k1.w);
-                            if (A.noise != nullptr) nz = ld4(NZ + 4 * lane);
-                        } else {
-                            const CF32 cf = coef_c + (size_t)step * 8;
-                            c0 = cf[0]; c1 = cf[1]; c2 = cf[2]; c3 = cf[3]; c4 = cf[4]; c5 = cf[5]; clip = cf[6]; ptype = cf[7];
-                            if (A.noise != nullptr) nz = ld4(A.noise + ((size_t)step * A.B + b) * 256 + 4 * lane);
-                        }
-                        const float4 lat = ld4(KEEP + 4 * lane);
-                        const float xs[4] = {lat.x, lat.y, lat.z, lat.w}, es4[4] = {e.x, e.y, e.z, e.w}, ns[4] = {nz.x, nz.y, nz.z, nz.w};
-                        float o[4];
-                        if constexpr (GRP) {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) o[i] = cl_sched_elem(i == 3, xs[i], es4[i], ns[i], c0, c1, c2, c3, c4, c5, clip, ptype);
-                        } else {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                float x0, ep;
-                                if (ptype == 0.f) { ep = es4[i]; x0 = (xs[i] - c1 * ep) / c0; }
-                                else              { x0 = es4[i]; ep = (xs[i] - c0 * x0) / c1; }
-                                if (clip != 0.f) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-                                o[i] = c2 * x0 + c3 * ep + c5 * xs[i] + c4 * ns[i];
-                            }
-                        }
-                        const float4 nl = make_float4(o[0], o[1], o[2], o[3]);
+                        if (A.noise != nullptr) nz = ld4(GRP ? NZ + 4 * lane : sched_noise_row(A.noise, A.B, step, b, lane));
+                        const float4 nl = sched_step(ld4(KEEP + 4 * lane), e, nz, k);
                         st4(KEEP + 4 * lane, nl);
                         xr = f4_add(nl, ld4(CONSTV + 4 * lane));
                         put_x<WT, 1>(XA, 0, 0, lane, xr);
@@ -1341,7 +1299,7 @@ static int launch_den_cluster_c(const ClArgs& ka, int C, bool q, hipStream_t st,
 static int den_cluster_ms_dispatch(const SeemeDenoiserWeights* w, const SeemeDenCluster* cl, const SeemeSampleArgs* a, ClArgs& ka, hipStream_t st, bool zeroed);   // den_cluster_ms.inc.hip
 
 extern "C" int seeme_denoiser_sample_cluster(const SeemeDenoiserWeights* w, const SeemeDenCluster* cl, const SeemeSampleArgs* a, void* stream) {
-    if (a->B <= 0) return seeme_fail("denoiser_sample_cluster: B must be > 0");
+    if (int rc = den_check_sample_args("denoiser_sample_cluster", a)) return rc;
     if (a->N < 1 || a->N > DCL_MAX_N) return seeme_fail("denoiser_sample_cluster: 1 or 2 condition tokens");
     const bool q = a->N > 1;
     if (!q && (a->catab == nullptr || a->force_query)) return seeme_fail("denoiser_sample_cluster: one condition token needs its ca table");
@@ -1349,8 +1307,6 @@ extern "C" int seeme_denoiser_sample_cluster(const SeemeDenoiserWeights* w, cons
     if (w->nhead != 1 || !w->sa_fold) return seeme_fail("denoiser_sample_cluster: one attention head (folded out_proj)");
     if (a->cfg || a->save != nullptr) return seeme_fail("denoiser_sample_cluster: no CFG pair, no training forward");
     if (w->ff_sa != FF_SA || w->ff != FF_D) return seeme_fail("denoiser_sample_cluster: built for sa ff 1024 / ffn_dim 128");
-    if (a->sched == SEEME_SCHED_NONE && a->steps != 1) return seeme_fail("denoiser_sample_cluster: SCHED_NONE needs steps == 1");
-    if (a->steps < 1) return seeme_fail("denoiser_sample_cluster: steps must be >= 1");
     const bool ms = cl->samples > 1;
     if (cl->xchg == nullptr || (!ms && cl->xchg_bytes < seeme_den_cluster_xchg_bytes(a->B, cl->C))) return seeme_fail("denoiser_sample_cluster: exchange buffer too small");
     if (((uintptr_t)cl->xchg & 15) != 0) return seeme_fail("denoiser_sample_cluster: exchange buffer must be 16-byte aligned");

@@ -257,9 +257,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster_ms(const ClArgs ka)
     const float sa_scale = 1.f / 16.f;
 
     typedef const __attribute__((address_space(4))) int32_t* CI32;
-    typedef const __attribute__((address_space(4))) float* CF32;
     const CI32 trow_c = (CI32)(uintptr_t)A.trow;
-    const CF32 coef_c = (CF32)(uintptr_t)A.coef;
     int row = trow_c[0];
 
     // ---- prologue
@@ -763,22 +761,10 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_cluster_ms(const ClArgs ka)
                     if (A.sched == SEEME_SCHED_NONE) {
                         st4(KEEP + es * 256 + 4 * lane, e);
                     } else {
-                        const CF32 cf = coef_c + (size_t)step * 8;
-                        const float c0 = cf[0], c1 = cf[1], c2 = cf[2], c3 = cf[3], c4 = cf[4], c5 = cf[5], clip = cf[6], ptype = cf[7];
+                        const SchedCoef k = sched_coef_row(A.coef, step);
                         float4 nz = make_float4(0.f, 0.f, 0.f, 0.f);
-                        if (A.noise != nullptr) nz = ld4(A.noise + ((size_t)step * A.B + bs) * 256 + 4 * lane);
-                        const float4 lat = ld4(KEEP + es * 256 + 4 * lane);
-                        const float xs[4] = {lat.x, lat.y, lat.z, lat.w}, es4[4] = {e.x, e.y, e.z, e.w}, ns[4] = {nz.x, nz.y, nz.z, nz.w};
-                        float o[4];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            float x0, ep;
-                            if (ptype == 0.f) { ep = es4[i]; x0 = (xs[i] - c1 * ep) / c0; }
-                            else              { x0 = es4[i]; ep = (xs[i] - c0 * x0) / c1; }
-                            if (clip != 0.f) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-                            o[i] = c2 * x0 + c3 * ep + c5 * xs[i] + c4 * ns[i];
-                        }
-                        const float4 nl = make_float4(o[0], o[1], o[2], o[3]);
+                        if (A.noise != nullptr) nz = ld4(sched_noise_row(A.noise, A.B, step, bs, lane));
+                        const float4 nl = sched_step(ld4(KEEP + es * 256 + 4 * lane), e, nz, k);
                         st4(KEEP + es * 256 + 4 * lane, nl);
                         xr = f4_add(nl, ld4(CONSTV + 4 * lane));
                         clm_put4<WT, NARROW>(XA, es, lane, xr);

@@ -18,6 +18,7 @@
 #include "den_layout.h"
 #include "lds_ring.hpp"
 #include "den_train.h"
+#include "den_sched.hpp"
 #include <utility>
 
 #define DEN_THREADS 512
@@ -639,12 +640,10 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_sample(const DenKArgs ka) {
     if (epi) st4(keep, xr);
 
     // ---- prologue: constants, layer 0 operands, first input vector, first DEN_R chunks
-    // per-step scalars (table row, scheduler coefficients) through the constant address space: scalar loads, which do
+    // per-step scalars (table row; scheduler coefficients: sched_coef_row) through the constant address space: scalar loads, which do
     // not queue behind (and whose waits do not drain) the vector-memory weight ring
     typedef const __attribute__((address_space(4))) int32_t* CI32;
-    typedef const __attribute__((address_space(4))) float* CF32;
     const CI32 trow_c = (CI32)(uintptr_t)A.trow;
-    const CF32 coef_c = (CF32)(uintptr_t)A.coef;
     int row = A.trow_per_sample ? trow_c[b] : trow_c[0];
     {
         for (int i = tid0; i < 192; i += DEN_THREADS)
@@ -929,22 +928,10 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_sample(const DenKArgs ka) {
                     if (epi) st4(keep, e);
                 } else if (epi) {
                     // ---- scheduler.step (mld.py:495-497; scalars prepared by seeme_amd/schedulers.py)
-                    const CF32 c = coef_c + (size_t)step * 8;
-                    const float c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3], c4 = c[4], c5 = c[5], clip = c[6], ptype = c[7];
+                    const SchedCoef k = sched_coef_row(A.coef, step);
                     float4 nz = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (A.noise != nullptr) nz = ld4(A.noise + ((size_t)step * A.B + bl) * 256 + 4 * lane);
-                    const float4 lat = ld4(keep);
-                    const float xs[4] = {lat.x, lat.y, lat.z, lat.w}, es4[4] = {e.x, e.y, e.z, e.w}, ns[4] = {nz.x, nz.y, nz.z, nz.w};
-                    float o[4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        float x0, ep;
-                        if (ptype == 0.f) { ep = es4[i]; x0 = (xs[i] - c1 * ep) / c0; }
-                        else              { x0 = es4[i]; ep = (xs[i] - c0 * x0) / c1; }
-                        if (clip != 0.f) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-                        o[i] = c2 * x0 + c3 * ep + c5 * xs[i] + c4 * ns[i];
-                    }
-                    const float4 nl = make_float4(o[0], o[1], o[2], o[3]);
+                    if (A.noise != nullptr) nz = ld4(sched_noise_row(A.noise, A.B, step, bl, lane));
+                    const float4 nl = sched_step(ld4(keep), e, nz, k);
                     st4(keep, nl);
                     xr = f4_add(nl, ld4(CONSTV + 4 * lane));                         // next step: sample + query_pos
                     put_x<WT, MS>(XB, es, 0, lane, xr);
@@ -1005,14 +992,29 @@ static int launch_den_wt(const DenKArgs& ka, bool fold, hipStream_t st) {
     return pair ? launch_den_ms<WT, 2>(ka, fold, st) : launch_den_ms<WT, 1>(ka, fold, st);
 }
 
+// What seeme_denoiser_sample and seeme_denoiser_sample_cluster (den_cluster.inc.hip) ask of SeemeSampleArgs alike, checked before anything
+// else: a forgotten table is an error string, not a device fault.  `who` labels the message with the entry point.
+static int den_check_sample_args(const char* who, const SeemeSampleArgs* a) {
+    const char* what = nullptr;
+    if (a->B <= 0) what = "B must be > 0";
+    else if (a->steps < 1) what = "steps must be >= 1";
+    else if (a->sched != SEEME_SCHED_NONE && a->sched != SEEME_SCHED_DDIM && a->sched != SEEME_SCHED_DDPM) what = "sched must be SEEME_SCHED_NONE, _DDIM or _DDPM";
+    else if (a->sched == SEEME_SCHED_NONE && a->steps != 1) what = "SCHED_NONE needs steps == 1";
+    else if (a->sched != SEEME_SCHED_NONE && a->coef == nullptr) what = "a scheduler needs its coefficient table (coef)";
+    else if (a->latents == nullptr || a->out == nullptr) what = "latents and out must not be NULL";
+    else if (a->ttab == nullptr || a->trow == nullptr || a->ctab == nullptr) what = "ttab, trow and ctab must not be NULL";
+    if (what == nullptr) return 0;
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return seeme_fail(msg);
+}
+
 extern "C" int seeme_denoiser_sample(const SeemeDenoiserWeights* w, const SeemeSampleArgs* a, void* stream) {
-    if (a->B <= 0) return seeme_fail("denoiser_sample: B must be > 0");
+    if (int rc = den_check_sample_args("denoiser_sample", a)) return rc;
     if (a->N < 1 || a->N > DEN_MAXTOK - 2) return seeme_fail("denoiser_sample: 1 <= N <= 4 condition tokens");
     if (w->nhead != 1 && w->nhead != 2 && w->nhead != 4) return seeme_fail("denoiser_sample: nhead must be 1, 2 or 4");
     if (w->ff_sa != FF_SA || w->ff != FF_D) return seeme_fail("denoiser_sample: built for sa ff 1024 / ffn_dim 128 (all reference configs)");
     if (w->layout == nullptr) return seeme_fail("denoiser_sample: layout table missing");
-    if (a->sched == SEEME_SCHED_NONE && a->steps != 1) return seeme_fail("denoiser_sample: SCHED_NONE needs steps == 1");
-    if (a->steps < 1) return seeme_fail("denoiser_sample: steps must be >= 1");
     if (a->save != nullptr && (a->steps != 1 || a->cfg || w->sa_fold || w->wdtype != 0 || !(a->N > 1 || a->force_query) || !a->trow_per_sample))
         return seeme_fail("denoiser_sample: save needs one step, no CFG, the unfolded fp32 image, the query GEMV and per-sample rows");
     DenKArgs ka;

@@ -127,12 +127,12 @@ def test_sample_pairs_every_branch(dev, monkeypatch):
 
 
 def test_wave_group_body_against_eight_wave_body(dev, monkeypatch):
-    """test_gpu_cluster_groups.py asserts that the two-wave-group body of k_den_cluster (C = 8, fp16 image: coefficients from LDS, the sums
-    spelled out in cl_sched_elem) gives the bits of the eight-wave body (k_den_cluster_ms forced to "8,2": scalar-loaded coefficients,
-    contraction left to the compiler) -- on the epsilon / no-clamp branch, which is the one cl_sched_elem was spelled for.  Here the same
-    pair runs every case at B = 2.  Only the float64 bound is asserted for each of the two; whether the bits agree is printed per case.
-    Measured on an MI355X: the bits agree in all twelve cases -- sample prediction, the clamp, c5 != 0 and the noise term included -- so
-    cl_sched_elem matches the compiler's contraction on the new branches as well.  Neither body was changed for that."""
+    """test_gpu_cluster_groups.py asserts that the two-wave-group body of k_den_cluster (C = 8, fp16 image: coefficients and noise row
+    from LDS) gives the bits of the eight-wave body (k_den_cluster_ms forced to "8,2": scalar-loaded coefficients) -- on the epsilon /
+    no-clamp branch.  Here the same pair runs every case at B = 2: sample prediction, the clamp, c5 != 0 and the noise term included.
+    Both bodies close the step with the one sched_step of csrc/den_sched.hpp, whose sums are spelled out and not left to the compiler,
+    and what they feed it is bit-identical by test_gpu_cluster_groups.py: so the bits must agree in all twelve cases, next to the
+    float64 bound for each of the two."""
     body = "cluster8_B2"
     b = R.BODIES[body]
     for case in R.one_step_cases(body) + R.chain_cases(body):
@@ -147,6 +147,7 @@ def test_wave_group_body_against_eight_wave_body(dev, monkeypatch):
         print(f"sched pair | {case['name']}: bits agree {np.array_equal(grp, ms)}, max |grp - ms| {float(np.abs(grp - ms).max()):.3e}, "
               f"rel err two wave groups {eg:.3e}, eight waves {em:.3e}, bound {case['tol']:.3g}")
         assert eg < case["tol"] and em < case["tol"], (case["name"], eg, em)
+        assert np.array_equal(grp, ms), case["name"]
 
 
 @pytest.mark.parametrize("body", ["sample_fp32", "cluster8_B2", "cluster4_B2"])

@@ -61,6 +61,42 @@ def test_call_labels_a_failure_with_the_entry_point():
     assert "seeme_pa_mpjpe_frames" in str(e.value) and "F must" in str(e.value)
 
 
+_BAD_SAMPLE_ARGS = {
+    "scheduler without coef": (dict(coef=None), "coefficient table"),
+    "sched = 3": (dict(sched=3), "sched must be"),
+    "steps = 0": (dict(steps=0), "steps must be >= 1"),
+    "SCHED_NONE with two steps": (dict(sched=0, steps=2), "SCHED_NONE needs steps == 1"),
+    "latents NULL": (dict(latents=None), "latents and out"),
+    "out NULL": (dict(out=None), "latents and out"),
+}
+
+
+@pytest.mark.parametrize("entry", ["seeme_denoiser_sample", "seeme_denoiser_sample_cluster"])
+@pytest.mark.parametrize("case", sorted(_BAD_SAMPLE_ARGS))
+def test_sample_entry_points_share_one_argument_check(entry, case):
+    """What both sampling entry points ask of SeemeSampleArgs is checked before anything else, by one function that labels the message
+    with the entry point: a scheduler without its coefficient table, an unknown scheduler, no step, SCHED_NONE with more than one step,
+    no latents, no output.  Weights and cluster are all-zero structs and the table pointers address one host float that nothing may read,
+    so a case that got past the shared check would fail on the per-entry ones with another message -- never reach a launch."""
+    from seeme_amd import _lib
+    lib = _lib.lib()
+    host = (C.c_float * 1)()
+    p = C.addressof(host)
+    a = _lib.SampleArgs()
+    a.B, a.N, a.steps, a.sched, a.guidance_scale = 2, 1, 2, _lib.SCHED_DDIM, 1.0
+    a.latents, a.ctab, a.ttab, a.trow, a.coef, a.out = p, p, p, p, p, p
+    fields, what = _BAD_SAMPLE_ARGS[case]
+    for k, v in fields.items():
+        setattr(a, k, v)
+    w, cl = _lib.DenoiserWeights(), _lib.DenCluster()
+    args = (C.byref(w), C.byref(a), None) if entry == "seeme_denoiser_sample" else (C.byref(w), C.byref(cl), C.byref(a), None)
+    assert getattr(lib, entry)(*args) != 0
+    msg = lib.seeme_last_error().decode()
+    assert msg.startswith(entry[len("seeme_"):] + ": ") and what in msg, msg
+    with pytest.raises(_lib.SeemeError, match=entry):
+        _lib.call(entry, *args)
+
+
 def test_workspace_grows_only_and_holds_one_buffer_per_key():
     from seeme_amd import _lib
     cpu = torch.device("cpu")
