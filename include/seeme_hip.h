@@ -720,6 +720,33 @@ int seeme_track_cost(const float* jts, const int32_t* idx, int Lf, int S, float 
 int seeme_track_filter(const float* pose, const float* transl, const int32_t* idx, int Lf, int L, int J,
                        const float* taps_host, int R, float* pose_out, float* transl_out, void* stream);
 
+/* ------------------------------------------------------------------ the headset's own path (csrc/headset.hip)
+ * A recording from a head-worn device carries the device's position in every frame: the only label-free evidence about where the
+ * wearer went.  The head is SMPL joint SEEME_HEAD_JOINT.  fp32, no atomics, fixed summation order: bitwise reproducible.
+ *
+ * How far a hypothesis' head strays from the SHAPE of the device's path over its window.  jts [W,K,T,24,3] (metres, in the frame the
+ * path is in), path [W,T,3] (row w: the device's positions at window w's frames, then anything), lengths [W] int32 on the device.
+ * With n = min(max(lengths[w], 0), T), h_t = jts[w,k,t,15], r_t = h_t - path[w,t] and o = (1/n) sum_{t<n} r_t:
+ *     cost[w,k] = 1000 x (1/n) sum_{t<n} |r_t - o|   (mm; 0 for n <= 1)
+ * The mean offset o is removed per hypothesis, so a constant offset between head and device costs nothing.  Two passes in this order
+ * (the mean, then the deviations from it); one wave per (w, k), a lane adds its frames t = lane, lane + 64, ... in increasing t and
+ * the 64 partial sums are added by a butterfly (distances 32, 16, .. 1).  Frames t >= n and joints other than 15 are never read.
+ * cost [W,K], usable as the unary term of seeme_path_select.  1 <= W <= 65536, 1 <= K <= 32, 1 <= T <= 2^20. */
+#define SEEME_HEAD_JOINT 15
+int seeme_head_path_cost(const float* jts, const float* path, const int32_t* lengths, int W, int K, int T, float* cost, void* stream);
+
+/* The shift that puts the head of ONE motion onto the device's path, smoothed.  joints [L,24,3], path [L,3]; taps_host [R+1] on the
+ * HOST, 0 <= R <= SEEME_HEAD_ANCHOR_RMAX, taps[0] > 0, every tap finite and >= 0 (validated; they reach the kernel by value:
+ * seeme_amd/track.py gaussian_taps).  With r[n] = path[n] - joints[n,15]:
+ *     shift[n]    = (sum_d taps[|d|] r[n+d]) / (sum_d taps[|d|])   over -R <= d <= R with 0 <= n+d < L, both sums in increasing d
+ *     residual[n] = 1000 x |r[n] - shift[n]|                        (mm)
+ * so the filter renormalises at the recording's two ends.  taps = {1} (R = 0) gives shift = r and residual = 0 exactly.  shift [L,3],
+ * residual [L]; 1 <= L <= 2^20.  One workgroup per 256 output frames holds r of its 256 + 2R frames in LDS; the result depends
+ * neither on the tiling nor on what the outputs held before. */
+#define SEEME_HEAD_ANCHOR_RMAX 30
+int seeme_head_anchor(const float* joints, const float* path, int L, const float* taps_host, int R, float* shift, float* residual,
+                      void* stream);
+
 /* ------------------------------------------------------------------ scene views of a moving camera (csrc/scene_views.hip)
  * The view-dependent selection of a scene mesh's vertices that the EgoBody scene tables are made with (EgoHMR
  * preprocess_scene_s1.py:91-114: into the camera frame, keep z > 0, every k-th survivor, the first P), for W views in one call.

@@ -479,10 +479,22 @@ def predict_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=N
     g.add_argument("--save_hypotheses", action="store_true", help="also store m_rst_all [W,K,T,F], every window's K hypotheses")
     g.add_argument("--video", type=str, default=None, help="decoded frames, uint8 RGB [Lf,H,W,3] as a .npy (opened memory-mapped), in "
                    "place of the recording's video key; the recording holds center, scale and, for Lf < L, video_index")
+    h = p.add_argument_group("the headset's own path (head_path, or the centres of world2cam; INTEGRATION.md K)")
+    h.add_argument("--head_weight", type=float, default=None, help="override TEST.PATH_HEAD_WEIGHT: weight of the head-path term (mm) "
+                   "when one hypothesis per window is chosen (0 = off)")
+    h.add_argument("--anchor_headset", action="store_true", help="set TEST.HEAD_ANCHOR: shift the stitched motion's head onto the path")
+    h.add_argument("--anchor_sigma", type=float, default=None, help="override TEST.HEAD_ANCHOR_SIGMA: Gaussian width of the shift's "
+                   "filter, frames (0..10)")
     p.set_defaults(frames=None)                                         # the window length: MOTION_LENGTH unless --frames says otherwise
     p.set_defaults(scene_points=None)                                   # rows of a scene view: TEST.SCENE_VIEW_POINTS unless given
     args = p.parse_args(argv)
     cfg = load_cfg(args, "test")
+    if args.head_weight is not None:
+        cfg.TEST.PATH_HEAD_WEIGHT = args.head_weight
+    if args.anchor_headset:
+        cfg.TEST.HEAD_ANCHOR = True
+    if args.anchor_sigma is not None:
+        cfg.TEST.HEAD_ANCHOR_SIGMA = args.anchor_sigma
     if args.scene_points is not None:
         cfg.TEST.SCENE_VIEW_POINTS = args.scene_points
     args.scene_points = int(cfg.TEST.get("SCENE_VIEW_POINTS", 20000))
@@ -514,10 +526,22 @@ def predict_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=N
     frames = made[3] if moving else None
     torch.manual_seed(int(cfg.SEED_VALUE) if args.seed is None else args.seed)
     betas = torch.from_numpy(rec["wearer_betas"]).to(dev) if "wearer_betas" in rec else None
+    head_path = None
+    if model.path_head_weight > 0 or model.head_anchor:                 # the device's position per frame, in the world frame
+        if "head_path" in rec:
+            head_path = rec["head_path"]
+        elif moving:
+            head_path = R.camera_centres(rec["world2cam"])
+        else:
+            raise ValueError(f"{args.input}: --head_weight / --anchor_headset need the headset's path: the recording holds neither "
+                             "head_path [L,3] nor world2cam [L,4,4] (whose camera centres are the path)")
     out = model.predict_recording(batch, rec["n_frames"], overlap=O, betas=betas,
-                                  window_frames=frames["world2cam"].float() if moving else None)
+                                  window_frames=frames["world2cam"].float() if moving else None, head_path=head_path)
     nb = 69 if model.name_dataset == "egobody" else 63
     res = {k: v.float().cpu().numpy() for k, v in motion_to_smpl(out["motion"], model.data_type, model.transl_in_feats, nb).items()}
+    if "transl" in out:                                                 # anchored: for features without a translation the shift alone
+        res["transl"] = out["transl"].float().cpu().numpy()
+    res.update({k: out[k].cpu().numpy() for k in ("head_cost", "head_shift", "head_residual") if k in out})
     res.update(joints=out["joints"].cpu().numpy(), window_starts=np.asarray(starts, np.int64), path=out["path"].cpu().numpy(),
                seam_cost=out["seam_cost"].cpu().numpy())
     if moving:                                                          # everything above is in the recording's world frame

@@ -391,6 +391,16 @@ class MLD(nn.Module):
         if isinstance(self.path_medoid_weight, bool) or not isinstance(self.path_medoid_weight, (int, float)) \
                 or not 0 <= self.path_medoid_weight < float("inf"):
             raise ValueError(f"TEST.PATH_MEDOID_WEIGHT must be a finite number >= 0, got {self.path_medoid_weight!r}")
+        # the headset's own path (predict_recording with head_path): the weight of the head-path term of the unary (0: off), whether
+        # the stitched motion is shifted onto the path, and the Gaussian width of that shift's filter (frames; a choice, not tuned)
+        self.path_head_weight = cfg.TEST.get("PATH_HEAD_WEIGHT", 0.0)
+        if isinstance(self.path_head_weight, bool) or not isinstance(self.path_head_weight, (int, float)) \
+                or not 0 <= self.path_head_weight < float("inf"):
+            raise ValueError(f"TEST.PATH_HEAD_WEIGHT must be a finite number >= 0, got {self.path_head_weight!r}")
+        self.head_anchor = cfg.TEST.get("HEAD_ANCHOR", False)
+        if not isinstance(self.head_anchor, bool):
+            raise ValueError(f"TEST.HEAD_ANCHOR must be true or false, got {self.head_anchor!r}")
+        self.head_anchor_sigma = check_sigma(cfg.TEST.get("HEAD_ANCHOR_SIGMA", DEFAULT_SIGMA), "TEST.HEAD_ANCHOR_SIGMA")
         # estimate.py --track (seeme_amd/track.py): the random walk's step (mm per frame), the weight of the flow's density against the
         # transitions and the Gaussian width of the filter (frames).  None of the three was tuned on data.
         self.track_step_mm = check_step_mm(cfg.TEST.get("TRACK_STEP_MM", DEFAULT_STEP_MM), "TEST.TRACK_STEP_MM")
@@ -1304,7 +1314,8 @@ class MLD(nn.Module):
 
     @torch.no_grad()
     def predict_recording(self, batch_of_windows, n_frames, overlap=None, betas=None, medoid_weight=None, num_hypotheses=None,
-                          latents=None, cond_noise=None, step_noise=None, window_frames=None):
+                          latents=None, cond_noise=None, step_noise=None, window_frames=None, head_path=None, head_weight=None,
+                          head_anchor=None, anchor_sigma=None):
         """One motion for a recording of `n_frames` frames.  The batch rows are its W windows (``recording.window_plan`` of n_frames,
         the batch's T and `overlap`; ``recording.windows_batch`` builds them), all in ONE coordinate frame unless `window_frames` says
         otherwise: the seam cost compares global joint positions (GIMO scenes are in one frame already; a moving camera: below).  Steps: ``predict`` (K hypotheses per window) -> ``overlap_cost`` -> unary[w,k] = medoid_weight x
@@ -1321,8 +1332,19 @@ class MLD(nn.Module):
         M_w before the seams are compared, the chosen windows' features are re-framed the same way (the orientation, and the
         translation when the features carry it: ``recording.reframe_smpl`` / ``reframe_rot6d``) before they are stitched, and motion,
         joints and seam_cost are in the world frame; ``predict``'s result stays in the windows' frames and the result gains
-        window_frames.  The medoid term is invariant under a rigid map and is taken as it is."""
+        window_frames.  The medoid term is invariant under a rigid map and is taken as it is.
+
+        head_path [n_frames,3]: the headset's position in every frame, in the frame the seams are compared in (the world frame with
+        window_frames; ``recording.camera_centres``).  Given alone it changes nothing.  head_weight (None = TEST.PATH_HEAD_WEIGHT, 0)
+        > 0 adds head_weight x ``head_path_cost`` (mm: how far a hypothesis' head strays from the shape of the headset's path over
+        its window) to the unary; the result gains head_cost [W,K] and head_cost_path [W].  It needs features that carry a
+        translation: other hypotheses have no global position to compare.  head_anchor (None = TEST.HEAD_ANCHOR, false) shifts the
+        stitched motion's head onto the path: shift, residual = ``head_anchor`` of the stitched joints with the taps of anchor_sigma
+        (None = TEST.HEAD_ANCHOR_SIGMA); joints and, where the features carry one, the motion's translation move by shift, and the
+        result gains head_shift [n_frames,3], head_residual [n_frames] (mm) and transl [n_frames,3] (the motion's translation, or
+        the shift alone for features without one).  The device sits a few centimetres from joint 15; that lever arm is not modelled."""
         from . import recording as R
+        from .track import gaussian_taps
         feats_ref, _t, _b, _u, _s, _i, length, _ = split_batch(self.condition, batch_of_windows)
         W, T = int(feats_ref.shape[0]), int(feats_ref.shape[1])
         O = overlap if overlap is not None else (self.window_overlap if self.window_overlap is not None else T // 4)
@@ -1336,6 +1358,27 @@ class MLD(nn.Module):
         if isinstance(mw, bool) or not isinstance(mw, (int, float)) or not 0 <= mw < float("inf"):
             raise ValueError(f"medoid_weight must be a finite number >= 0, got {mw!r}")
         dev = feats_ref.device
+        hw = self.path_head_weight if head_weight is None else head_weight
+        if isinstance(hw, bool) or not isinstance(hw, (int, float)) or not 0 <= hw < float("inf"):
+            raise ValueError(f"head_weight must be a finite number >= 0, got {hw!r}")
+        anchor = self.head_anchor if head_anchor is None else head_anchor
+        if not isinstance(anchor, bool):
+            raise ValueError(f"head_anchor must be true or false, got {anchor!r}")
+        sigma = self.head_anchor_sigma if anchor_sigma is None else check_sigma(anchor_sigma, "anchor_sigma")
+        if (hw > 0 or anchor) and head_path is None:
+            raise ValueError("predict_recording: head_weight > 0 and head_anchor need head_path [n_frames,3], the headset's position in "
+                             "every frame (recording.camera_centres of world2cam, or the recording's head_path)")
+        if hw > 0 and not self.transl_in_feats:
+            raise ValueError("predict_recording: head_weight (TEST.PATH_HEAD_WEIGHT) > 0 needs features that carry a translation "
+                             "(TRAIN.ABLATION.PREDICT_TRANSL, not rot6d): these hypotheses have no global position to compare with the "
+                             "headset's path; head_anchor places them")
+        hp = None
+        if head_path is not None:
+            hp = torch.as_tensor(head_path)
+            if tuple(hp.shape) != (n_frames, 3) or not hp.dtype.is_floating_point:
+                raise ValueError(f"predict_recording: head_path is {tuple(hp.shape)} {hp.dtype}: expected floats [n_frames,3] = "
+                                 f"[{n_frames},3]")
+            hp = hp.to(device=dev, dtype=torch.float32).contiguous()
         if betas is not None:
             betas = torch.as_tensor(betas, device=dev, dtype=torch.float32)
             if betas.dim() == 1:
@@ -1357,6 +1400,10 @@ class MLD(nn.Module):
         unary = None
         if mw > 0:
             unary = (float(mw) / max(K - 1, 1)) * pr["hyp_metrics"]["PAIR_DIST"].sum(dim=2)
+        head_cost = None
+        if hw > 0:                                                             # (jts: the frame the path is in)
+            head_cost = R.head_path_cost_hip(jts.contiguous(), R.head_path_windows(hp, starts, lens, int(jts.shape[2])), lens)
+            unary = float(hw) * head_cost if unary is None else unary + float(hw) * head_cost
         sel = R.path_select_hip(cost, unary)
         chosen = pr["m_rst_all"][torch.arange(W, device=dev), sel["path"]].contiguous()          # [W,T,F]
         if window_frames is not None:
@@ -1377,6 +1424,16 @@ class MLD(nn.Module):
                "window_starts": starts, "window_lengths": lens, "predict": pr}
         if window_frames is not None:
             out["window_frames"] = Mw
+        if head_cost is not None:
+            out["head_cost"] = head_cost
+            out["head_cost_path"] = head_cost[torch.arange(W, device=dev), sel["path"]]
+        if anchor:
+            shift, residual = R.head_anchor_hip(joints.contiguous(), hp, gaussian_taps(sigma))
+            out["joints"] = joints + shift[:, None]
+            if self.transl_in_feats:
+                motion[:, -3:] += shift
+            out["head_shift"], out["head_residual"] = shift, residual
+            out["transl"] = motion[:, -3:].clone() if self.transl_in_feats else shift
         return out
 
     def forward(self, batch, **kw):

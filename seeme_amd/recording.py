@@ -17,6 +17,11 @@ The model sees clips of T frames; a recording is cut into W overlapping windows 
                        k-th survivor, the first P) for W camera poses in one call; ``scene_views_torch`` is its twin.
 ``reframe_smpl`` / ``reframe_rot6d`` / ``reframe_joints``: a rigid map p -> A p + a applied to SMPL parameters and to joints, plain torch.
 
+``head_path_cost_hip`` ``seeme_head_path_cost``: cost [W,K] (mm), how far a hypothesis' head (joint 15) strays from the shape of the
+                       headset's own path over its window, the mean offset removed: a unary term of ``path_select``.
+``head_anchor_hip``    ``seeme_head_anchor``: the smoothed shift [L,3] that puts the stitched motion's head onto the headset's path,
+                       and what is left per frame (mm).  ``camera_centres`` / ``head_path_windows`` prepare the path on the host.
+
 ``load_recording`` / ``windows_batch`` read a recording ``.npz`` and cut it into a batch with the data module's tuple
 layout whose wearer slot is zero; a recording may carry its image condition as raw video frames, whose patches around the interactee
 are then cut by ``crops.crop_patches_hip`` (``choose_frames``: which stored frame serves a window).  The definitions are stated once,
@@ -37,6 +42,8 @@ NLERP_DOT = 0.9995           # SEEME_STITCH_NLERP_DOT
 SCENE_VIEW_TILE = 1024               # SEEME_SCENE_VIEW_TILE: vertices of one workgroup of seeme_scene_views
 SCENE_VIEW_WINDOWS_PER_PASS = 16     # SEEME_SCENE_VIEW_WINDOWS_PER_PASS: views a workgroup walks over its tile
 SCENE_VIEW_POINTS = 20000            # rows of an EgoBody scene table (TEST.SCENE_VIEW_POINTS)
+HEAD_JOINT = 15                      # SEEME_HEAD_JOINT: the SMPL head, as EgoMetrics uses it
+HEAD_ANCHOR_RMAX = 30                # SEEME_HEAD_ANCHOR_RMAX: ceil(3 x track.SIGMA_MAX)
 
 
 # ----------------------------------------------------------------------------- window plan (host)
@@ -197,6 +204,108 @@ def stitch_windows_torch(feats, overlap: int, n_frames: int, layout: int) -> tor
             y = torch.cat([y, a[:, nr:] + u[:, 0] * (b[:, nr:] - a[:, nr:])], dim=1)
     out[ov] = y
     return out
+
+
+# ----------------------------------------------------------------------------- the headset's own path: host side and twins
+def camera_centres(world2cam) -> np.ndarray:
+    """world2cam [L,4,4], the rigid maps p -> A_n p + a_n -> float64 [L,3]: c[n] = -A_n^T a_n, the device's position in the world frame.
+    Only the centre is used, so no convention about the camera's axes enters."""
+    M = np.asarray(world2cam, np.float64)
+    if M.ndim != 3 or M.shape[1:] != (4, 4):
+        raise ValueError(f"camera_centres: world2cam is {M.shape}: expected [L,4,4]")
+    return -np.einsum("nji,nj->ni", M[:, :3, :3], M[:, :3, 3])
+
+
+def check_head_path(path, n_frames: int, what: str = "head_path") -> np.ndarray:
+    """head_path -> float64 [L,3]: floats, finite, one row per recording frame, or a ValueError that names the key."""
+    a = path.detach().cpu().numpy() if isinstance(path, torch.Tensor) else np.asarray(path)
+    if a.dtype.kind != "f" or a.shape != (n_frames, 3):
+        raise ValueError(f"{what}: head_path is {a.shape} {a.dtype}: expected floats [{n_frames},3] (L = {n_frames}), the device's "
+                         "position in the recording's world frame")
+    if not np.isfinite(a).all():
+        raise ValueError(f"{what}: head_path of frame {int(np.argmax(~np.isfinite(a).all(axis=1)))} is not finite")
+    return np.ascontiguousarray(a, np.float64)
+
+
+def head_path_windows(path, starts, lengths, T: int) -> torch.Tensor:
+    """path [L,3] (tensor or array) -> [W,T,3] in its dtype (on its device): row w holds path[starts[w] : starts[w] + lengths[w]], then
+    zeros: the path operand of ``head_path_cost`` for the windows of ``window_plan``."""
+    p = path if isinstance(path, torch.Tensor) else torch.from_numpy(np.asarray(path))
+    if p.dim() != 2 or p.shape[1] != 3:
+        raise ValueError(f"head_path_windows: the path is {tuple(p.shape)}: expected [L,3]")
+    T = int(T)
+    out = torch.zeros(len(starts), T, 3, dtype=p.dtype, device=p.device)
+    for w, (lo, ln) in enumerate(zip(starts, lengths)):
+        lo, ln = int(lo), int(ln)
+        if lo < 0 or ln < 0 or ln > T or lo + ln > p.shape[0]:
+            raise ValueError(f"head_path_windows: window {w} (frames {lo}..{lo + ln - 1}) does not fit T = {T} and a path of {p.shape[0]} frames")
+        out[w, :ln] = p[lo:lo + ln]
+    return out
+
+
+def _check_head_cost(jts, path, lengths):
+    if not isinstance(jts, torch.Tensor) or not isinstance(path, torch.Tensor) or not jts.dtype.is_floating_point or path.dtype != jts.dtype:
+        raise ValueError(f"head_path_cost: joints and path must be float tensors of one dtype, got {getattr(jts, 'dtype', type(jts))} and "
+                         f"{getattr(path, 'dtype', type(path))}")
+    if jts.dim() != 5 or tuple(jts.shape[3:]) != (24, 3) or tuple(path.shape) != (jts.shape[0], jts.shape[2], 3):
+        raise ValueError(f"head_path_cost: joints are {tuple(jts.shape)}, the path is {tuple(path.shape)}: expected [W,K,T,24,3] and [W,T,3]")
+    n = lengths.detach().cpu().reshape(-1).tolist() if isinstance(lengths, torch.Tensor) else [v for v in lengths]
+    if len(n) != jts.shape[0] or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in n):
+        raise ValueError(f"head_path_cost: lengths are {n!r}: expected {jts.shape[0]} integers, one per window")
+    return [int(v) for v in n]
+
+
+def head_path_cost_torch(jts, path, lengths) -> torch.Tensor:
+    """jts [W,K,T,24,3], path [W,T,3], lengths [W] (integers), any float dtype, any device, any K -> cost [W,K] (mm): the definition of
+    ``seeme_head_path_cost``.  Frames past a window's length take no part (a NaN there is not seen)."""
+    n = _check_head_cost(jts, path, lengths)
+    W, K, T = (int(v) for v in jts.shape[:3])
+    nn = torch.tensor(n, device=jts.device).clamp(0, T)
+    keep = (torch.arange(T, device=jts.device)[None] < nn[:, None])[:, None, :, None]                 # [W,1,T,1]
+    div = nn.clamp(min=1).to(jts.dtype)[:, None]
+    r = torch.where(keep, jts[:, :, :, HEAD_JOINT] - path[:, None], torch.zeros((), dtype=jts.dtype, device=jts.device))
+    o = r.sum(dim=2) / div[..., None]                                                                  # [W,K,3]
+    dev = torch.where(keep[..., 0], (r - o[:, :, None]).norm(dim=-1), torch.zeros((), dtype=jts.dtype, device=jts.device))
+    cost = 1000.0 * (dev.sum(dim=2) / div)
+    return torch.where((nn > 1)[:, None], cost, torch.zeros_like(cost))
+
+
+def _host_taps(taps, what: str) -> np.ndarray:
+    t = np.asarray(taps.detach().cpu().numpy() if isinstance(taps, torch.Tensor) else taps)
+    if t.ndim != 1 or t.shape[0] < 1 or t.dtype.kind not in "fiu":
+        raise ValueError(f"{what}: taps are {t.shape} {t.dtype}: expected numbers [R+1]")
+    return t
+
+
+def _check_head_anchor(joints, path):
+    if not isinstance(joints, torch.Tensor) or not isinstance(path, torch.Tensor) or not joints.dtype.is_floating_point \
+            or path.dtype != joints.dtype:
+        raise ValueError(f"head_anchor: joints and path must be float tensors of one dtype, got {getattr(joints, 'dtype', type(joints))} "
+                         f"and {getattr(path, 'dtype', type(path))}")
+    if joints.dim() != 3 or tuple(joints.shape[1:]) != (24, 3) or joints.shape[0] < 1 or tuple(path.shape) != (joints.shape[0], 3):
+        raise ValueError(f"head_anchor: joints are {tuple(joints.shape)}, the path is {tuple(path.shape)}: expected [L,24,3] and [L,3], "
+                         "L >= 1")
+
+
+def head_anchor_torch(joints, path, taps) -> Tuple[torch.Tensor, torch.Tensor]:
+    """joints [L,24,3], path [L,3], any float dtype, any device; taps [R+1] (``track.gaussian_taps``), any R -> (shift [L,3], residual
+    [L] in mm): the definition of ``seeme_head_anchor``."""
+    _check_head_anchor(joints, path)
+    tp = _host_taps(taps, "head_anchor").astype(np.float64)
+    if not np.isfinite(tp).all() or (tp < 0).any() or not tp[0] > 0:
+        raise ValueError(f"head_anchor: every tap must be finite and >= 0 and taps[0] > 0, got {tp.tolist()}")
+    Rr, n_fr = tp.shape[0] - 1, int(joints.shape[0])
+    tp = torch.from_numpy(tp).to(device=joints.device, dtype=joints.dtype)
+    r = path - joints[:, HEAD_JOINT]
+    n = torch.arange(n_fr, device=joints.device)
+    acc, wsum = torch.zeros_like(r), torch.zeros(n_fr, device=joints.device, dtype=joints.dtype)
+    for d in range(-Rr, Rr + 1):                                                 # increasing frame order
+        m = n + d
+        k = tp[abs(d)] * ((m >= 0) & (m < n_fr)).to(joints.dtype)
+        acc = acc + k[:, None] * r[m.clamp(0, n_fr - 1)]
+        wsum = wsum + k
+    shift = acc / wsum[:, None]
+    return shift, 1000.0 * (r - shift).norm(dim=-1)
 
 
 # ----------------------------------------------------------------------------- scene views: the twin
@@ -372,6 +481,51 @@ def stitch_windows_hip(feats, overlap: int, n_frames: int, layout: int) -> torch
     return out
 
 
+def head_path_cost_hip(jts, path, lengths) -> torch.Tensor:
+    """jts [W,K,T,24,3], path [W,T,3] fp32 on the device, K <= 32 (``head_path_cost_torch`` serves K > 32), lengths [W] integers ->
+    cost [W,K] (mm) (``seeme_head_path_cost``).  Launches on the current stream."""
+    n = _check_head_cost(jts, path, lengths)
+    if jts.dtype != torch.float32:
+        raise ValueError(f"head_path_cost: joints and path must be float32, got {jts.dtype}")
+    L.require_cuda(jts, "jts")
+    L.require_cuda(path, "path")
+    W, K, T = (int(v) for v in jts.shape[:3])
+    len32 = torch.tensor(n, dtype=torch.int64).clamp(-1, T).to(device=jts.device, dtype=torch.int32)
+    return _launch_head_cost(jts.contiguous(), path.contiguous(), len32, W, K, T)
+
+
+def _launch_head_cost(jts, path, len32, W, K, T, out=None) -> torch.Tensor:
+    """out: the cost tensor to write into (the tests' slot); None operands travel as null pointers."""
+    cost = out if out is not None else torch.empty(max(W, 0), max(K, 0), device=jts.device, dtype=torch.float32)
+    L.call("seeme_head_path_cost", L.ptr(jts), L.ptr(path), L.ptr(len32), W, K, T, L.ptr(cost), L.current_stream())
+    return cost
+
+
+def head_anchor_hip(joints, path, taps) -> Tuple[torch.Tensor, torch.Tensor]:
+    """joints [L,24,3], path [L,3] fp32 on the device, taps [R+1] on the host, R <= 30 (the library validates them) -> (shift [L,3],
+    residual [L] in mm) (``seeme_head_anchor``).  Launches on the current stream."""
+    _check_head_anchor(joints, path)
+    if joints.dtype != torch.float32:
+        raise ValueError(f"head_anchor: joints and path must be float32, got {joints.dtype}")
+    L.require_cuda(joints, "joints")
+    L.require_cuda(path, "path")
+    tp = _host_taps(taps, "head_anchor").astype(np.float32)
+    return _launch_head_anchor(joints.contiguous(), path.contiguous(), int(joints.shape[0]), tp, tp.shape[0] - 1)
+
+
+def _launch_head_anchor(joints, path, n_frames, taps, Rr, out=None):
+    """taps: float32 numpy on the host or None; out: (shift, residual) to write into (the tests' slots)."""
+    import ctypes as C
+    dev = (joints if joints is not None else path).device
+    if out is None:
+        out = (torch.empty(max(n_frames, 0), 3, device=dev, dtype=torch.float32), torch.empty(max(n_frames, 0), device=dev, dtype=torch.float32))
+    if taps is not None:
+        taps = np.ascontiguousarray(taps, np.float32)
+    L.call("seeme_head_anchor", L.ptr(joints), L.ptr(path), n_frames, None if taps is None else taps.ctypes.data_as(C.POINTER(C.c_float)),
+           Rr, L.ptr(out[0]), L.ptr(out[1]), L.current_stream())
+    return out
+
+
 def scene_views_hip(verts, world2view, P: int) -> Dict[str, torch.Tensor]:
     """verts [N,3], world2view [W,4,4] fp32 on the device -> cloud [W,P,3], index [W,P] int32, count [W] int32
     (``seeme_scene_views``).  Launches on the current stream and does not synchronise."""
@@ -538,7 +692,9 @@ def load_recording(path: str, video: Optional[str] = None, require_interactee: b
     body_pose [L,69|63], transl [L,3], betas [10]; optionally scene [P,3], image_feats [L,2048], wearer_betas [10].  float32.
     A moving camera adds world2cam [L,4,4], the rigid map from the recording's world frame to every frame's camera frame (float64:
     it is composed and inverted), and, in place of scene, scene_vertices [N,3]: the scene's vertices in the world frame, from which
-    every window's view is selected (``scene_views_hip``).
+    every window's view is selected (``scene_views_hip``).  head_path [L,3] (floats, finite; returned float64) is the device's position
+    in the world frame; when present it is used instead of the centres of world2cam (``camera_centres``), and it also serves
+    recordings in one fixed frame that have no world2cam.
 
     The image condition has ONE source: image_feats, or video [Lf,H,W,3] uint8 RGB (decoded frames; needs center [L,2] and scale
     [L], the interactee's box per recording frame, ``crops.patch_box``), or image_crops [Lf,224,224,3] uint8 (patches already cut).
@@ -566,6 +722,7 @@ def load_recording(path: str, video: Optional[str] = None, require_interactee: b
                if k in z.files}
         if "world2cam" in z.files:
             rec["world2cam"] = np.asarray(z["world2cam"], np.float64)
+        head_path = z["head_path"] if "head_path" in z.files else None
         rec.update({k: z[k] for k in _FRAME_KEYS if k in z.files})
     if video is not None:
         if "video" in rec:
@@ -593,6 +750,8 @@ def load_recording(path: str, video: Optional[str] = None, require_interactee: b
         raise ValueError(f"{path}: scene_vertices need world2cam: a view is selected per camera pose")
     if "world2cam" in rec:
         check_world2cam(rec["world2cam"], n, path)
+    if head_path is not None:
+        rec["head_path"] = check_head_path(head_path, n, path)
     if not require_interactee:
         _check_estimate_input(rec, n, path, bool(allow_sparse))
     rec["n_frames"] = n
