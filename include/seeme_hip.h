@@ -747,6 +747,31 @@ int seeme_head_path_cost(const float* jts, const float* path, const int32_t* len
 int seeme_head_anchor(const float* joints, const float* path, int L, const float* taps_host, int R, float* shift, float* residual,
                       void* stream);
 
+/* ------------------------------------------------------------------ the body against the scene, per candidate frame (csrc/scene_depth.hip)
+ * How deep a hypothesis reaches into the scene's points, from the joints alone: the body is NB capsules (one per bone), the scene one
+ * cloud shared by every window.  jts [W,K,T,J,3] (metres), lengths [W] int32 on the device, points [N,3] in the frame jts is in;
+ * segs_host [NB,2] int32 (joint indices in 0..J-1; equal ends: a sphere) and radius_host [NB] (finite, >= 0) on the HOST, validated
+ * there, by value in the kernel arguments; 1 <= NB <= SEEME_SCENE_DEPTH_NBMAX.  With n = min(max(lengths[w], 0), T), for a frame
+ * f = (w,k,t), t < n, a point p and a segment b:
+ *     a = jts[f,segs[b,0]], c = jts[f,segs[b,1]], e = c - a, q = p - a, ee = e.e
+ *     s = ee > 0 ? clamp((q.e) / ee, 0, 1) : 0,  v = q - s e,  dist = sqrt(v.v)
+ *     depth[w,k,t] = 1000 x max(0, max over p < N, b < NB of (radius[b] - dist))   (mm; 0 for t >= n)
+ *     cost[w,k]    = (1/n) sum_{t<n} depth[w,k,t]                                  (mm; 0 for n = 0)
+ *     hits[w,k]    = the number of frames t < n with depth > 0                     (int32)
+ * A pair whose value is NaN contributes nothing.  Frames t >= n and joints that no segment names are never read.  The kernel
+ * multiplies by 1/ee where the definition divides.  max is exact and free of order and ONE expression evaluates a (frame, point,
+ * segment) triple, so depth is bit for bit independent of the order of the points, of N under appended points out of reach, of W, K
+ * and T as a layout of the same frames, and of the culling, which skips only triples whose computed value is <= 0.  cost adds depth
+ * in fp32, one wave per (w,k): a lane adds t = lane, lane + 64, ... in increasing t, the 64 partial sums by a butterfly (distances
+ * 32 .. 1), as seeme_head_path_cost does.  cost is usable as a unary term of seeme_path_select.
+ * 1 <= W <= 65536, 1 <= K <= 32, 1 <= T <= 2^20, 1 <= N <= 2^24, 1 <= J <= 32, and W x K x ceil(T / SEEME_SCENE_DEPTH_CHUNK) < 2^24
+ * (the launch's workgroups).  depth [W,K,T], cost [W,K], hits [W,K] int32.  No workspace, no allocation, no synchronisation. */
+#define SEEME_SCENE_DEPTH_NBMAX 32
+#define SEEME_SCENE_DEPTH_CHUNK 32
+int seeme_scene_depth(const float* jts, const int32_t* lengths, const float* points, int W, int K, int T, int J, int N,
+                      const int32_t* segs_host, const float* radius_host, int NB, float* depth, float* cost, int32_t* hits,
+                      void* stream);
+
 /* ------------------------------------------------------------------ scene views of a moving camera (csrc/scene_views.hip)
  * The view-dependent selection of a scene mesh's vertices that the EgoBody scene tables are made with (EgoHMR
  * preprocess_scene_s1.py:91-114: into the camera frame, keep z > 0, every k-th survivor, the first P), for W views in one call.

@@ -485,6 +485,13 @@ def predict_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=N
     h.add_argument("--anchor_headset", action="store_true", help="set TEST.HEAD_ANCHOR: shift the stitched motion's head onto the path")
     h.add_argument("--anchor_sigma", type=float, default=None, help="override TEST.HEAD_ANCHOR_SIGMA: Gaussian width of the shift's "
                    "filter, frames (0..10)")
+    s = p.add_argument_group("the body against the scene (scene_vertices, or scene; INTEGRATION.md K)")
+    s.add_argument("--scene_weight", type=float, default=None, help="override TEST.PATH_SCENE_WEIGHT: weight of the body-scene term "
+                   "(mm of penetration) when one hypothesis per window is chosen (0 = off)")
+    s.add_argument("--scene_report", action="store_true", help="set TEST.SCENE_REPORT: also write scene_depth [L], the stitched "
+                   "motion's penetration per frame (mm)")
+    s.add_argument("--scene_quantile", type=float, default=None, help="override TEST.SCENE_CAPSULE_QUANTILE: quantile of the "
+                   "template's distances that gives a capsule's radius (0..1)")
     p.set_defaults(frames=None)                                         # the window length: MOTION_LENGTH unless --frames says otherwise
     p.set_defaults(scene_points=None)                                   # rows of a scene view: TEST.SCENE_VIEW_POINTS unless given
     args = p.parse_args(argv)
@@ -495,6 +502,12 @@ def predict_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=N
         cfg.TEST.HEAD_ANCHOR = True
     if args.anchor_sigma is not None:
         cfg.TEST.HEAD_ANCHOR_SIGMA = args.anchor_sigma
+    if args.scene_weight is not None:
+        cfg.TEST.PATH_SCENE_WEIGHT = args.scene_weight
+    if args.scene_report:
+        cfg.TEST.SCENE_REPORT = True
+    if args.scene_quantile is not None:
+        cfg.TEST.SCENE_CAPSULE_QUANTILE = args.scene_quantile
     if args.scene_points is not None:
         cfg.TEST.SCENE_VIEW_POINTS = args.scene_points
     args.scene_points = int(cfg.TEST.get("SCENE_VIEW_POINTS", 20000))
@@ -516,6 +529,12 @@ def predict_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=N
         log.info("EMA weights over %d tensors", overlay_ema(model, ck, ckpt))
     model = model.to(dev).eval()
     rec = R.load_recording(args.input, video=args.video)
+    scene_cloud = None
+    if model.path_scene_weight > 0 or model.scene_report:               # the scene's points, in the recording's common frame
+        scene_cloud = rec.get("scene_vertices", rec.get("scene"))
+        if scene_cloud is None:
+            raise ValueError(f"{args.input}: --scene_weight / --scene_report need the scene's points: the recording holds neither "
+                             "scene_vertices [N,3] nor scene [P,3]")
     O = model.window_overlap if model.window_overlap is not None else T // 4
     moving = "world2cam" in rec                                         # every window in the camera frame of its first frame
     pelvis = R.rest_pelvis(model.smpl_model, torch.from_numpy(rec["betas"]).to(dev)[None])[0] if moving else None
@@ -536,12 +555,14 @@ def predict_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=N
             raise ValueError(f"{args.input}: --head_weight / --anchor_headset need the headset's path: the recording holds neither "
                              "head_path [L,3] nor world2cam [L,4,4] (whose camera centres are the path)")
     out = model.predict_recording(batch, rec["n_frames"], overlap=O, betas=betas,
-                                  window_frames=frames["world2cam"].float() if moving else None, head_path=head_path)
+                                  window_frames=frames["world2cam"].float() if moving else None, head_path=head_path,
+                                  scene_cloud=scene_cloud)
     nb = 69 if model.name_dataset == "egobody" else 63
     res = {k: v.float().cpu().numpy() for k, v in motion_to_smpl(out["motion"], model.data_type, model.transl_in_feats, nb).items()}
     if "transl" in out:                                                 # anchored: for features without a translation the shift alone
         res["transl"] = out["transl"].float().cpu().numpy()
-    res.update({k: out[k].cpu().numpy() for k in ("head_cost", "head_shift", "head_residual") if k in out})
+    res.update({k: out[k].cpu().numpy() for k in ("head_cost", "head_shift", "head_residual", "scene_cost", "scene_hits", "scene_depth")
+                if k in out})
     res.update(joints=out["joints"].cpu().numpy(), window_starts=np.asarray(starts, np.int64), path=out["path"].cpu().numpy(),
                seam_cost=out["seam_cost"].cpu().numpy())
     if moving:                                                          # everything above is in the recording's world frame
@@ -558,9 +579,10 @@ def predict_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=N
     os.makedirs(d, exist_ok=True)
     with open(args.output, "wb") as f:                                  # (np.savez would append .npz to a bare name)
         np.savez(f, **res)
-    log.info("%d frames in %d windows of %d (overlap %d), %d hypotheses each; mean seam cost %.1f mm; written to %s", rec["n_frames"],
+    scene_note = f"; mean scene cost of the path {float(out['scene_cost_path'].mean()):.2f} mm" if "scene_cost_path" in out else ""
+    log.info("%d frames in %d windows of %d (overlap %d), %d hypotheses each; mean seam cost %.1f mm%s; written to %s", rec["n_frames"],
              len(starts), T, O, int(out["predict"]["m_rst_all"].shape[1]),
-             float(out["seam_cost"].mean()) if len(starts) > 1 else 0.0, args.output)
+             float(out["seam_cost"].mean()) if len(starts) > 1 else 0.0, scene_note, args.output)
     return {"file": args.output, "n_frames": rec["n_frames"], "windows": len(starts), "path": out["path"].tolist(),
             "path_cost": float(out["path_cost"])}
 

@@ -20,5 +20,5 @@ int seeme_check_launch(const char* kernel) {
     }
     return 0;
 }
-extern "C" int seeme_version(void) { return 101; }
+extern "C" int seeme_version(void) { return 102; }
 extern "C" const char* seeme_last_error(void) { return g_err; }

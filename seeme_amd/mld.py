@@ -401,6 +401,19 @@ class MLD(nn.Module):
         if not isinstance(self.head_anchor, bool):
             raise ValueError(f"TEST.HEAD_ANCHOR must be true or false, got {self.head_anchor!r}")
         self.head_anchor_sigma = check_sigma(cfg.TEST.get("HEAD_ANCHOR_SIGMA", DEFAULT_SIGMA), "TEST.HEAD_ANCHOR_SIGMA")
+        # the body against the scene (predict_recording with scene_cloud): the weight of the body-scene term of the unary (0: off),
+        # whether the stitched motion's depth per frame is reported, and the quantile of the default capsules' radii
+        self.path_scene_weight = cfg.TEST.get("PATH_SCENE_WEIGHT", 0.0)
+        if isinstance(self.path_scene_weight, bool) or not isinstance(self.path_scene_weight, (int, float)) \
+                or not 0 <= self.path_scene_weight < float("inf"):
+            raise ValueError(f"TEST.PATH_SCENE_WEIGHT must be a finite number >= 0, got {self.path_scene_weight!r}")
+        self.scene_report = cfg.TEST.get("SCENE_REPORT", False)
+        if not isinstance(self.scene_report, bool):
+            raise ValueError(f"TEST.SCENE_REPORT must be true or false, got {self.scene_report!r}")
+        self.scene_capsule_quantile = cfg.TEST.get("SCENE_CAPSULE_QUANTILE", 0.5)
+        if isinstance(self.scene_capsule_quantile, bool) or not isinstance(self.scene_capsule_quantile, (int, float)) \
+                or not 0 <= self.scene_capsule_quantile <= 1:
+            raise ValueError(f"TEST.SCENE_CAPSULE_QUANTILE must be a number in 0..1, got {self.scene_capsule_quantile!r}")
         # estimate.py --track (seeme_amd/track.py): the random walk's step (mm per frame), the weight of the flow's density against the
         # transitions and the Gaussian width of the filter (frames).  None of the three was tuned on data.
         self.track_step_mm = check_step_mm(cfg.TEST.get("TRACK_STEP_MM", DEFAULT_STEP_MM), "TEST.TRACK_STEP_MM")
@@ -1315,7 +1328,7 @@ class MLD(nn.Module):
     @torch.no_grad()
     def predict_recording(self, batch_of_windows, n_frames, overlap=None, betas=None, medoid_weight=None, num_hypotheses=None,
                           latents=None, cond_noise=None, step_noise=None, window_frames=None, head_path=None, head_weight=None,
-                          head_anchor=None, anchor_sigma=None):
+                          head_anchor=None, anchor_sigma=None, scene_cloud=None, scene_weight=None, scene_report=None, capsules=None):
         """One motion for a recording of `n_frames` frames.  The batch rows are its W windows (``recording.window_plan`` of n_frames,
         the batch's T and `overlap`; ``recording.windows_batch`` builds them), all in ONE coordinate frame unless `window_frames` says
         otherwise: the seam cost compares global joint positions (GIMO scenes are in one frame already; a moving camera: below).  Steps: ``predict`` (K hypotheses per window) -> ``overlap_cost`` -> unary[w,k] = medoid_weight x
@@ -1342,7 +1355,17 @@ class MLD(nn.Module):
         stitched motion's head onto the path: shift, residual = ``head_anchor`` of the stitched joints with the taps of anchor_sigma
         (None = TEST.HEAD_ANCHOR_SIGMA); joints and, where the features carry one, the motion's translation move by shift, and the
         result gains head_shift [n_frames,3], head_residual [n_frames] (mm) and transl [n_frames,3] (the motion's translation, or
-        the shift alone for features without one).  The device sits a few centimetres from joint 15; that lever arm is not modelled."""
+        the shift alone for features without one).  The device sits a few centimetres from joint 15; that lever arm is not modelled.
+
+        scene_cloud [N,3]: the scene's points in the frame the seams are compared in (the world frame with window_frames).  Given
+        alone it changes nothing and launches nothing.  scene_weight (None = TEST.PATH_SCENE_WEIGHT, 0) > 0 adds scene_weight x the
+        cost of ``recording.scene_depth_hip`` (mm: how deep the capsules round a hypothesis' bones reach into the cloud, the mean
+        over its window) to the unary; the result gains scene_cost [W,K], scene_hits [W,K] (frames that penetrate) and
+        scene_cost_path [W].  Like head_weight it needs features that carry a translation.  scene_report (None = TEST.SCENE_REPORT,
+        false) runs the same kernel on the final joints (after the anchoring, if any) as one row of n_frames frames; the result
+        gains scene_depth [n_frames] (mm).  capsules: (segs [NB,2], radius [NB]); None = ``recording.body_capsules`` of the model's
+        SMPL with the betas and TEST.SCENE_CAPSULE_QUANTILE (0.5).  The proxy leaves out the feet, the skull above joint 15 and the
+        interactee's body, and a cloud only holds what was seen."""
         from . import recording as R
         from .track import gaussian_taps
         feats_ref, _t, _b, _u, _s, _i, length, _ = split_batch(self.condition, batch_of_windows)
@@ -1372,6 +1395,25 @@ class MLD(nn.Module):
             raise ValueError("predict_recording: head_weight (TEST.PATH_HEAD_WEIGHT) > 0 needs features that carry a translation "
                              "(TRAIN.ABLATION.PREDICT_TRANSL, not rot6d): these hypotheses have no global position to compare with the "
                              "headset's path; head_anchor places them")
+        sw = self.path_scene_weight if scene_weight is None else scene_weight
+        if isinstance(sw, bool) or not isinstance(sw, (int, float)) or not 0 <= sw < float("inf"):
+            raise ValueError(f"scene_weight must be a finite number >= 0, got {sw!r}")
+        report = self.scene_report if scene_report is None else scene_report
+        if not isinstance(report, bool):
+            raise ValueError(f"scene_report must be true or false, got {report!r}")
+        if (sw > 0 or report) and scene_cloud is None:
+            raise ValueError("predict_recording: scene_weight > 0 and scene_report need scene_cloud [N,3], the scene's points in the "
+                             "frame the seams are compared in (the recording's scene_vertices, or its scene)")
+        if sw > 0 and not self.transl_in_feats:
+            raise ValueError("predict_recording: scene_weight (TEST.PATH_SCENE_WEIGHT) > 0 needs features that carry a translation "
+                             "(TRAIN.ABLATION.PREDICT_TRANSL, not rot6d): these hypotheses have no global position to compare with the "
+                             "scene's points")
+        cloud = None
+        if scene_cloud is not None and (sw > 0 or report):
+            cloud = torch.as_tensor(scene_cloud)
+            if cloud.dim() != 2 or cloud.shape[1] != 3 or cloud.shape[0] < 1 or not cloud.dtype.is_floating_point:
+                raise ValueError(f"predict_recording: scene_cloud is {tuple(cloud.shape)} {cloud.dtype}: expected floats [N,3], N >= 1")
+            cloud = cloud.to(device=dev, dtype=torch.float32).contiguous()
         hp = None
         if head_path is not None:
             hp = torch.as_tensor(head_path)
@@ -1404,6 +1446,16 @@ class MLD(nn.Module):
         if hw > 0:                                                             # (jts: the frame the path is in)
             head_cost = R.head_path_cost_hip(jts.contiguous(), R.head_path_windows(hp, starts, lens, int(jts.shape[2])), lens)
             unary = float(hw) * head_cost if unary is None else unary + float(hw) * head_cost
+        scene = None
+        if cloud is not None:
+            if capsules is None:                                               # (rot6d is posed with zero betas)
+                capsules = R.body_capsules(self.smpl_model, None if betas is None or self.data_type == "rot6d" else betas[0],
+                                           float(self.scene_capsule_quantile))
+            if not isinstance(capsules, (tuple, list)) or len(capsules) != 2:
+                raise ValueError("predict_recording: capsules must be (segs [NB,2], radius [NB])")
+        if sw > 0:                                                             # (jts: the frame the cloud is in)
+            scene = R.scene_depth_hip(jts.contiguous(), lens, cloud, capsules[0], capsules[1])
+            unary = float(sw) * scene["cost"] if unary is None else unary + float(sw) * scene["cost"]
         sel = R.path_select_hip(cost, unary)
         chosen = pr["m_rst_all"][torch.arange(W, device=dev), sel["path"]].contiguous()          # [W,T,F]
         if window_frames is not None:
@@ -1434,6 +1486,12 @@ class MLD(nn.Module):
                 motion[:, -3:] += shift
             out["head_shift"], out["head_residual"] = shift, residual
             out["transl"] = motion[:, -3:].clone() if self.transl_in_feats else shift
+        if scene is not None:
+            out["scene_cost"], out["scene_hits"] = scene["cost"], scene["hits"]
+            out["scene_cost_path"] = scene["cost"][torch.arange(W, device=dev), sel["path"]]
+        if report:                                                             # the final joints as one row of n_frames frames
+            out["scene_depth"] = R.scene_depth_hip(out["joints"].contiguous()[None, None], [n_frames], cloud, capsules[0],
+                                                   capsules[1])["depth"][0, 0]
         return out
 
     def forward(self, batch, **kw):

@@ -21,6 +21,9 @@ The model sees clips of T frames; a recording is cut into W overlapping windows 
                        headset's own path over its window, the mean offset removed: a unary term of ``path_select``.
 ``head_anchor_hip``    ``seeme_head_anchor``: the smoothed shift [L,3] that puts the stitched motion's head onto the headset's path,
                        and what is left per frame (mm).  ``camera_centres`` / ``head_path_windows`` prepare the path on the host.
+``scene_depth_hip``    ``seeme_scene_depth``: depth [W,K,T] (mm), how deep the capsules round a hypothesis' bones (``body_capsules``)
+                       reach into the scene's points, its mean cost [W,K] (a unary term of ``path_select``) and the count of
+                       penetrating frames hits [W,K]; ``scene_depth_torch`` is its twin.
 
 ``load_recording`` / ``windows_batch`` read a recording ``.npz`` and cut it into a batch with the data module's tuple
 layout whose wearer slot is zero; a recording may carry its image condition as raw video frames, whose patches around the interactee
@@ -44,6 +47,9 @@ SCENE_VIEW_WINDOWS_PER_PASS = 16     # SEEME_SCENE_VIEW_WINDOWS_PER_PASS: views 
 SCENE_VIEW_POINTS = 20000            # rows of an EgoBody scene table (TEST.SCENE_VIEW_POINTS)
 HEAD_JOINT = 15                      # SEEME_HEAD_JOINT: the SMPL head, as EgoMetrics uses it
 HEAD_ANCHOR_RMAX = 30                # SEEME_HEAD_ANCHOR_RMAX: ceil(3 x track.SIGMA_MAX)
+SCENE_DEPTH_NBMAX = 32               # SEEME_SCENE_DEPTH_NBMAX: capsules of one table
+SCENE_DEPTH_CHUNK = 32               # SEEME_SCENE_DEPTH_CHUNK: frames of one workgroup of seeme_scene_depth
+CAPSULE_SKIP = (10, 11)              # the feet: standing on the floor is contact, the shin capsule ends at the ankle
 
 
 # ----------------------------------------------------------------------------- window plan (host)
@@ -308,6 +314,110 @@ def head_anchor_torch(joints, path, taps) -> Tuple[torch.Tensor, torch.Tensor]:
     return shift, 1000.0 * (r - shift).norm(dim=-1)
 
 
+# ----------------------------------------------------------------------------- the body against the scene: capsules and the twin
+def _segment_distance(p: np.ndarray, a: np.ndarray, c: np.ndarray) -> np.ndarray:
+    """Distance of the points p [V,3] from the segments a[b] .. c[b] ([NB,3] each) -> [V,NB], float64 on the host.  Where the closest
+    point is an end, the distance is taken from that joint itself: two bones that share the joint then tie exactly."""
+    e, q = c - a, p[:, None] - a[None]
+    ee = (e * e).sum(-1)
+    s = (np.clip((q * e[None]).sum(-1) / np.where(ee > 0, ee, 1.0), 0.0, 1.0) * (ee > 0))[..., None]
+    x = np.where(s <= 0, a[None], np.where(s >= 1, c[None], a[None] + s * e[None]))
+    return np.linalg.norm(p[:, None] - x, axis=-1)
+
+
+def body_capsules(smpl_model, betas=None, quantile: float = 0.5, segs=None) -> Tuple[np.ndarray, np.ndarray]:
+    """The capsule table of ``scene_depth``: (segs [NB,2] int32, radius [NB] float32), built on the host in float64.  segs defaults to
+    (parent[j], j) for j = 1..23 without the feet j = 10, 11: 21 bones.  The template is posed at rest with betas [10] (zeros if
+    None), every vertex goes to its nearest segment (the lowest b on a tie), and radius[b] is the `quantile` of the distances of b's
+    vertices, the lower one (a sample, never an interpolation); 0 for a segment without vertices, which never penetrates.  The
+    median keeps the capsule inside the body: the term under-reports rather than penalising contact."""
+    if isinstance(quantile, bool) or not isinstance(quantile, (int, float)) or not 0 <= quantile <= 1:
+        raise ValueError(f"body_capsules: quantile must be a number in 0..1, got {quantile!r}")
+    f64 = lambda t: t.detach().cpu().numpy().astype(np.float64)        # noqa: E731
+    v = f64(smpl_model.v_template)
+    if betas is not None:
+        b = np.asarray(betas.detach().cpu().numpy() if isinstance(betas, torch.Tensor) else betas, np.float64).reshape(-1)
+        if b.shape != (10,) or not np.isfinite(b).all():
+            raise ValueError(f"body_capsules: betas are {b.shape}: expected 10 finite numbers")
+        v = v + f64(smpl_model.shapedirs)[:, :, :10] @ b
+    jt = f64(smpl_model.J_regressor) @ v                               # [J,3]: at rest the joints are the regressed ones
+    if segs is None:
+        par = smpl_model.parents.detach().cpu().numpy()
+        segs = [(int(par[j]), j) for j in range(1, 24) if j not in CAPSULE_SKIP]
+    sg = np.asarray(segs)
+    if sg.ndim != 2 or sg.shape[1] != 2 or sg.shape[0] < 1 or sg.dtype.kind not in "iu" or sg.min() < 0 or sg.max() >= jt.shape[0]:
+        raise ValueError(f"body_capsules: segs must be joint indices [NB,2] in 0..{jt.shape[0] - 1}, got {sg.tolist()!r}")
+    d = _segment_distance(v, jt[sg[:, 0]], jt[sg[:, 1]])               # [V,NB]
+    own = d.argmin(axis=1)                                             # (the first of equal minima: the lowest b)
+    radius = np.zeros(sg.shape[0], np.float64)
+    for b in range(sg.shape[0]):
+        mine = np.sort(d[own == b, b])
+        if mine.size:
+            radius[b] = mine[int(np.floor(quantile * (mine.size - 1)))]
+    return sg.astype(np.int32), radius.astype(np.float32)
+
+
+def _check_scene_depth(jts, lengths, points, segs, radius):
+    """Shapes and dtypes of the operands of ``scene_depth``; -> (lengths as a list, or the int32 device tensor itself; segs [NB,2]
+    int32; radius [NB] float64), the two tables on the host."""
+    if not isinstance(jts, torch.Tensor) or not isinstance(points, torch.Tensor) or not jts.dtype.is_floating_point \
+            or points.dtype != jts.dtype:
+        raise ValueError(f"scene_depth: joints and points must be float tensors of one dtype, got {getattr(jts, 'dtype', type(jts))} "
+                         f"and {getattr(points, 'dtype', type(points))}")
+    if jts.dim() != 5 or jts.shape[4] != 3 or min(jts.shape) < 1 or points.dim() != 2 or points.shape[1] != 3 or points.shape[0] < 1:
+        raise ValueError(f"scene_depth: joints are {tuple(jts.shape)}, the points {tuple(points.shape)}: expected [W,K,T,J,3] and [N,3], "
+                         "nothing empty")
+    if points.device != jts.device:
+        raise ValueError(f"scene_depth: joints are on {jts.device}, the points on {points.device}")
+    sg = np.asarray(segs.detach().cpu().numpy() if isinstance(segs, torch.Tensor) else segs)
+    rd = np.asarray(radius.detach().cpu().numpy() if isinstance(radius, torch.Tensor) else radius)
+    if sg.ndim != 2 or sg.shape[1] != 2 or sg.shape[0] < 1 or sg.dtype.kind not in "iu" or rd.shape != (sg.shape[0],) \
+            or rd.dtype.kind not in "fiu":
+        raise ValueError(f"scene_depth: segs are {sg.shape} {sg.dtype}, radius is {rd.shape} {rd.dtype}: expected integers [NB,2] and "
+                         "numbers [NB], NB >= 1")
+    W = int(jts.shape[0])
+    if isinstance(lengths, torch.Tensor) and lengths.is_cuda and lengths.dtype == torch.int32 and tuple(lengths.shape) == (W,):
+        return lengths, sg.astype(np.int32), rd.astype(np.float64)     # on the device already: nothing is copied back
+    n = lengths.detach().cpu().reshape(-1).tolist() if isinstance(lengths, torch.Tensor) else [v for v in lengths]
+    if len(n) != W or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in n):
+        raise ValueError(f"scene_depth: lengths are {n!r}: expected {W} integers, one per window")
+    return [int(v) for v in n], sg.astype(np.int32), rd.astype(np.float64)
+
+
+def scene_depth_torch(jts, lengths, points, segs, radius, max_elems: int = 1 << 24) -> Dict[str, torch.Tensor]:
+    """jts [W,K,T,J,3], points [N,3] (any float dtype, any device), lengths [W] integers, segs [NB,2] joint indices and radius [NB]
+    (finite, >= 0; any NB) -> {"depth" [W,K,T] (mm), "cost" [W,K] (mm), "hits" [W,K] int32}: the definition of ``seeme_scene_depth``.
+    The points go through in chunks, so that no intermediate holds more than about `max_elems` (frame, segment, point) triples.
+    Frames past a window's length, joints that no segment names and pairs whose value is a NaN take no part."""
+    n, sg, rd = _check_scene_depth(jts, lengths, points, segs, radius)
+    W, K, T, J = (int(v) for v in jts.shape[:4])
+    if sg.min() < 0 or sg.max() >= J:
+        raise ValueError(f"scene_depth: every segment index must be in 0..J-1 = 0..{J - 1}, got {sg.tolist()}")
+    if not np.isfinite(rd).all() or (rd < 0).any():
+        raise ValueError(f"scene_depth: every radius must be finite and >= 0, got {rd.tolist()}")
+    dev, dt = jts.device, jts.dtype
+    nn = (n.to(torch.int64) if isinstance(n, torch.Tensor) else torch.tensor(n, device=dev)).clamp(0, T)
+    keep = (torch.arange(T, device=dev)[None] < nn[:, None])[:, None]                                # [W,1,T]
+    sgt = torch.from_numpy(sg.astype(np.int64)).to(dev)
+    r = torch.from_numpy(rd).to(device=dev, dtype=dt)
+    a = jts[:, :, :, sgt[:, 0]][..., None, :]                                                        # [W,K,T,NB,1,3]
+    e = jts[:, :, :, sgt[:, 1]][..., None, :] - a
+    ee = (e * e).sum(-1)                                                                             # [W,K,T,NB,1]
+    pos = ee > 0
+    one, zero, ninf = torch.ones((), dtype=dt, device=dev), torch.zeros((), dtype=dt, device=dev), \
+        torch.full((), float("-inf"), dtype=dt, device=dev)
+    best = torch.full((W, K, T), float("-inf"), dtype=dt, device=dev)
+    step = max(1, int(max_elems) // (W * K * T * sg.shape[0]))
+    for lo in range(0, int(points.shape[0]), step):
+        q = points[lo:lo + step] - a                                                                 # [W,K,T,NB,P,3]
+        s = torch.where(pos, ((q * e).sum(-1) / torch.where(pos, ee, one)).clamp(0, 1), zero)
+        val = r[:, None] - (q - s[..., None] * e).norm(dim=-1)                                       # [W,K,T,NB,P]
+        best = torch.maximum(best, torch.where(val != val, ninf, val).amax(dim=(-1, -2)))
+    depth = torch.where(keep, 1000.0 * best.clamp(min=0), zero)
+    cost = torch.where((nn > 0)[:, None], depth.sum(dim=2) / nn.clamp(min=1).to(dt)[:, None], zero)
+    return {"depth": depth, "cost": cost, "hits": (depth > 0).sum(dim=2).to(torch.int32)}
+
+
 # ----------------------------------------------------------------------------- scene views: the twin
 def _view_coord(M, c: int, x, y, z):
     """Coordinate c of the moved vertices, in the order of the kernel's fmaf chain (torch has no fused multiply-add: two roundings
@@ -523,6 +633,42 @@ def _launch_head_anchor(joints, path, n_frames, taps, Rr, out=None):
         taps = np.ascontiguousarray(taps, np.float32)
     L.call("seeme_head_anchor", L.ptr(joints), L.ptr(path), n_frames, None if taps is None else taps.ctypes.data_as(C.POINTER(C.c_float)),
            Rr, L.ptr(out[0]), L.ptr(out[1]), L.current_stream())
+    return out
+
+
+def scene_depth_hip(jts, lengths, points, segs, radius) -> Dict[str, torch.Tensor]:
+    """jts [W,K,T,J,3], points [N,3] fp32 on the device, lengths [W] integers (an int32 tensor on the device is taken as it is),
+    segs [NB,2] and radius [NB] on the host (NB <= 32, indices below J, radii finite and >= 0: the library validates them) ->
+    {"depth" [W,K,T] (mm), "cost" [W,K] (mm), "hits" [W,K] int32} (``seeme_scene_depth``).  Launches on the current stream and does
+    not synchronise; no workspace."""
+    n, sg, rd = _check_scene_depth(jts, lengths, points, segs, radius)
+    if jts.dtype != torch.float32:
+        raise ValueError(f"scene_depth: joints and points must be float32, got {jts.dtype}")
+    L.require_cuda(jts, "jts")
+    L.require_cuda(points, "points")
+    W, K, T, J = (int(v) for v in jts.shape[:4])
+    len32 = n if isinstance(n, torch.Tensor) else torch.tensor(n, dtype=torch.int64).clamp(-1, T).to(device=jts.device, dtype=torch.int32)
+    return _launch_scene_depth(jts.contiguous(), len32, points.contiguous(), W, K, T, J, int(points.shape[0]), sg, rd.astype(np.float32),
+                               sg.shape[0])
+
+
+def _launch_scene_depth(jts, len32, points, W, K, T, J, N, segs, radius, NB, out=None) -> Dict[str, torch.Tensor]:
+    """segs int32 [NB,2] / radius float32 [NB] numpy on the host, or None; out: {"depth", "cost", "hits"} to write into (the tests'
+    slots); None operands travel as null pointers."""
+    import ctypes as C
+    dev = next(t for t in (jts, points, len32) if t is not None).device
+    if out is None:
+        out = {"depth": torch.empty(max(W, 0), max(K, 0), max(T, 0), device=dev, dtype=torch.float32),
+               "cost": torch.empty(max(W, 0), max(K, 0), device=dev, dtype=torch.float32),
+               "hits": torch.empty(max(W, 0), max(K, 0), device=dev, dtype=torch.int32)}
+    if segs is not None:
+        segs = np.ascontiguousarray(segs, np.int32)
+    if radius is not None:
+        radius = np.ascontiguousarray(radius, np.float32)
+    L.call("seeme_scene_depth", L.ptr(jts), L.ptr(len32), L.ptr(points), W, K, T, J, N,
+           None if segs is None else segs.ctypes.data_as(C.POINTER(C.c_int32)),
+           None if radius is None else radius.ctypes.data_as(C.POINTER(C.c_float)), NB, L.ptr(out["depth"]), L.ptr(out["cost"]),
+           L.ptr(out["hits"]), L.current_stream())
     return out
 
 
