@@ -747,6 +747,34 @@ int seeme_head_path_cost(const float* jts, const float* path, const int32_t* len
 int seeme_head_anchor(const float* joints, const float* path, int L, const float* taps_host, int R, float* shift, float* residual,
                       void* stream);
 
+/* How far a hypothesis' head TURNS against the device over its window, up to a constant mount rotation.  A head-worn device also
+ * reports its orientation in every frame, and it is rigid with the head: seen from the head, its orientation does not change.
+ * feats [W,K,T,F] renormed features in one of seeme_stitch_windows' layouts: SEEME_STITCH_ANGLE (F = J x 3) and
+ * SEEME_STITCH_ANGLE_TRANSL (F = J x 3 + 3) with J >= 16 (EgoBody 72 / 75, GIMO 66 / 69), SEEME_STITCH_ROT6D (F = 144); another
+ * layout / F pair is refused by name.  dev_quat [W,T,4]: unit quaternions (w,x,y,z), the device's orientation (device -> the frame
+ * the features are in) at window w's frames, then anything; lengths [W] int32 on the device.  Per (w,k), with
+ * n = min(max(lengths[w], 0), T):
+ *     h_t  = the global rotation of joint SEEME_HEAD_JOINT: the quaternion product along the chain 0 -> 3 -> 6 -> 9 -> 12 -> 15, in
+ *            that order; a joint's quaternion is formed exactly as seeme_stitch_windows forms it (axis-angle v: (cos(|v|/2),
+ *            sin(|v|/2) v/|v|); rot6d: Gram-Schmidt, then of the rotation matrix, the largest of w, x, y, z first)
+ *     d_t  = conj(h_t) (x) dev_quat[w,t]           the device seen from the head: constant in t for a correct hypothesis, whatever
+ *                                                  the camera's axis convention
+ *     s_t  = -1 when d_t . d_0 < 0, otherwise +1
+ *     m    = sum_{t<n} s_t d_t, normalised         (m . d_0 >= 1: it never vanishes)
+ *     a_t  = 2 atan2(|vec(conj(m) (x) d_t)|, |scalar(conj(m) (x) d_t)|) x 180/pi
+ *     cost[w,k] = (1/n) sum_{t<n} a_t              (degrees; 0 for n <= 1)
+ * angle [W,K,T] (or NULL: not written) holds a_t, degrees per frame, and 0 for t >= n (all of it for n <= 1).  The constant m is
+ * removed per hypothesis, so a constant rotation between head and device (how the device is mounted, which way its axes point)
+ * costs nothing -- and cannot be observed.  Two passes in this order (m, then the angles against it); one wave per (w, k), a lane
+ * adds its frames t = lane, lane + 64, ... in increasing t, the 64 partial sums are added by the butterfly of seeme_head_path_cost
+ * and d_0 is broadcast from lane 0.  Only the six chain joints of the frames t < n are read; in the angle layouts the translation
+ * columns never.  cost [W,K], usable as a unary term of seeme_path_select.  1 <= W <= 65536, 1 <= K <= 32, 1 <= T <= 2^20.
+ * Against a float64 evaluation of this definition on the same fp32 inputs (chain rotations of about 0.4 rad per joint, 10 degrees
+ * of noise, T up to 196; 26 324 frames) the kernel on the MI355X is within 2.9e-6 relative per frame at angles >= 5 degrees and
+ * within 1.8e-5 degrees below that, and cost is within 1.5e-6 relative. */
+int seeme_head_rot_cost(const float* feats, int layout, int F, const float* dev_quat, const int32_t* lengths, int W, int K, int T,
+                        float* cost, float* angle /* or NULL */, void* stream);
+
 /* ------------------------------------------------------------------ the body against the scene, per candidate frame (csrc/scene_depth.hip)
  * How deep a hypothesis reaches into the scene's points, from the joints alone: the body is NB capsules (one per bone), the scene one
  * cloud shared by every window.  jts [W,K,T,J,3] (metres), lengths [W] int32 on the device, points [N,3] in the frame jts is in;

@@ -249,6 +249,7 @@ _SIGNATURES = {
     "seeme_track_filter": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, fp, fp, fp]),
     "seeme_head_path_cost": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, C.c_int, fp, fp]),
     "seeme_head_anchor": (C.c_int, [fp, fp, C.c_int, C.POINTER(C.c_float), C.c_int, fp, fp, fp]),
+    "seeme_head_rot_cost": (C.c_int, [fp, C.c_int, C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, fp, fp, fp]),
     "seeme_scene_depth": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float),
                                     C.c_int, fp, fp, fp, fp]),
     "seeme_scene_views_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

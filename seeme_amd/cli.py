@@ -485,6 +485,12 @@ def predict_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=N
     h.add_argument("--anchor_headset", action="store_true", help="set TEST.HEAD_ANCHOR: shift the stitched motion's head onto the path")
     h.add_argument("--anchor_sigma", type=float, default=None, help="override TEST.HEAD_ANCHOR_SIGMA: Gaussian width of the shift's "
                    "filter, frames (0..10)")
+    h.add_argument("--head_rot_weight", type=float, default=None, help="override TEST.PATH_HEAD_ROT_WEIGHT: weight of the head-rotation "
+                   "term (mm per degree the head turns against the device: head_rot, or the rotations of world2cam; 0 = off)")
+    h.add_argument("--head_rot_report", action="store_true", help="set TEST.HEAD_ROT_REPORT: also write head_rot_residual [L] and "
+                   "head_rot_mean, the stitched motion's head against the device's orientation (degrees)")
+    h.add_argument("--head_offset", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="override "
+                   "TEST.HEAD_DEVICE_OFFSET: the vector from joint 15 to the device in the device's frame, metres")
     s = p.add_argument_group("the body against the scene (scene_vertices, or scene; INTEGRATION.md K)")
     s.add_argument("--scene_weight", type=float, default=None, help="override TEST.PATH_SCENE_WEIGHT: weight of the body-scene term "
                    "(mm of penetration) when one hypothesis per window is chosen (0 = off)")
@@ -502,6 +508,12 @@ def predict_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=N
         cfg.TEST.HEAD_ANCHOR = True
     if args.anchor_sigma is not None:
         cfg.TEST.HEAD_ANCHOR_SIGMA = args.anchor_sigma
+    if args.head_rot_weight is not None:
+        cfg.TEST.PATH_HEAD_ROT_WEIGHT = args.head_rot_weight
+    if args.head_rot_report:
+        cfg.TEST.HEAD_ROT_REPORT = True
+    if args.head_offset is not None:
+        cfg.TEST.HEAD_DEVICE_OFFSET = list(args.head_offset)
     if args.scene_weight is not None:
         cfg.TEST.PATH_SCENE_WEIGHT = args.scene_weight
     if args.scene_report:
@@ -554,15 +566,24 @@ def predict_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=N
         else:
             raise ValueError(f"{args.input}: --head_weight / --anchor_headset need the headset's path: the recording holds neither "
                              "head_path [L,3] nor world2cam [L,4,4] (whose camera centres are the path)")
+    head_rot = None
+    if model.path_head_rot_weight > 0 or model.head_rot_report or (model.head_device_offset != 0).any():
+        if "head_rot" in rec:                                           # the device's orientation per frame, device -> world
+            head_rot = rec["head_rot"]
+        elif moving:
+            head_rot = R.camera_rotations(rec["world2cam"])
+        else:
+            raise ValueError(f"{args.input}: --head_rot_weight / --head_rot_report / --head_offset need the headset's orientation: the "
+                             "recording holds neither head_rot [L,3,3] nor world2cam [L,4,4] (whose rotations, transposed, are it)")
     out = model.predict_recording(batch, rec["n_frames"], overlap=O, betas=betas,
                                   window_frames=frames["world2cam"].float() if moving else None, head_path=head_path,
-                                  scene_cloud=scene_cloud)
+                                  scene_cloud=scene_cloud, head_rot=head_rot)
     nb = 69 if model.name_dataset == "egobody" else 63
     res = {k: v.float().cpu().numpy() for k, v in motion_to_smpl(out["motion"], model.data_type, model.transl_in_feats, nb).items()}
     if "transl" in out:                                                 # anchored: for features without a translation the shift alone
         res["transl"] = out["transl"].float().cpu().numpy()
-    res.update({k: out[k].cpu().numpy() for k in ("head_cost", "head_shift", "head_residual", "scene_cost", "scene_hits", "scene_depth")
-                if k in out})
+    res.update({k: out[k].cpu().numpy() for k in ("head_cost", "head_shift", "head_residual", "scene_cost", "scene_hits", "scene_depth",
+                                                  "head_rot_cost", "head_rot_residual", "head_rot_mean") if k in out})
     res.update(joints=out["joints"].cpu().numpy(), window_starts=np.asarray(starts, np.int64), path=out["path"].cpu().numpy(),
                seam_cost=out["seam_cost"].cpu().numpy())
     if moving:                                                          # everything above is in the recording's world frame
@@ -580,6 +601,8 @@ def predict_main(argv: Optional[List[str]] = None, datamodule=None, smpl_model=N
     with open(args.output, "wb") as f:                                  # (np.savez would append .npz to a bare name)
         np.savez(f, **res)
     scene_note = f"; mean scene cost of the path {float(out['scene_cost_path'].mean()):.2f} mm" if "scene_cost_path" in out else ""
+    if "head_rot_cost_path" in out:
+        scene_note += f"; mean rotation cost of the path {float(out['head_rot_cost_path'].mean()):.2f} degrees"
     log.info("%d frames in %d windows of %d (overlap %d), %d hypotheses each; mean seam cost %.1f mm%s; written to %s", rec["n_frames"],
              len(starts), T, O, int(out["predict"]["m_rst_all"].shape[1]),
              float(out["seam_cost"].mean()) if len(starts) > 1 else 0.0, scene_note, args.output)

@@ -1,8 +1,11 @@
 // headset.hip -- the headset's own path as evidence about the wearer: how far the head of every hypothesis strays from the shape of the
 // device's trajectory over its window (seeme_head_path_cost, a unary term of seeme_path_select) and the shift that puts the stitched
-// motion's head onto the device's path (seeme_head_anchor).  Definitions: include/seeme_hip.h; the plain-torch twins are in
-// seeme_amd/recording.py.  fp32 throughout, no atomics: every result is bitwise reproducible.
+// motion's head onto the device's path (seeme_head_anchor); and the headset's orientation: how far a hypothesis' head turns against
+// the device over its window, up to a constant mount rotation (seeme_head_rot_cost, a unary term as well).  Definitions:
+// include/seeme_hip.h; the plain-torch twins are in seeme_amd/recording.py.  fp32 throughout, no atomics: every result is bitwise
+// reproducible.
 #include "api_util.hpp"
+#include "rec_quat.hpp"
 #include <math.h>
 #include <stdint.h>
 
@@ -71,6 +74,93 @@ extern "C" int seeme_head_path_cost(const float* jts, const float* path, const i
     hipLaunchKernelGGL(k_head_path_cost, dim3((WK + HS_WAVES - 1) / HS_WAVES), dim3(HS_THREADS), 0, (hipStream_t)stream, jts, path,
                        lengths, WK, K, T, cost);
     return seeme_check_launch("k_head_path_cost");
+}
+
+// ------------------------------------------------------------------ head-rotation cost
+// h_t: the quaternion product along the chain 0 -> 3 -> 6 -> 9 -> 12 -> 15 (joint 3c, c = 0..5) of one frame's feature row; each joint
+// quaternion is the one seeme_stitch_windows forms (rec_quat.hpp).  Only these six units of the row are read.
+__device__ __forceinline__ RecQuat hs_head_quat(const float* row, bool rot6d) {
+    RecQuat h = rot6d ? rec_rot6d_to_quat(row) : rec_aa_to_quat(row);
+#pragma unroll
+    for (int c = 1; c <= SEEME_HEAD_JOINT / 3; ++c)
+        h = rec_mul(h, rot6d ? rec_rot6d_to_quat(row + 18 * c) : rec_aa_to_quat(row + 9 * c));
+    return h;
+}
+
+__device__ __forceinline__ RecQuat hs_shfl(RecQuat q, int src) {
+    return {__shfl(q.w, src), __shfl(q.x, src), __shfl(q.y, src), __shfl(q.z, src)};
+}
+
+// Partition: as k_head_path_cost, one wave per (w, k) and lane l on the frames t = l, l + 64, ... < n in increasing t.  Pass 1: d_t =
+// conj(h_t) (x) dev_t, the device seen from the head; d_0 comes from lane 0 by a shuffle, every d_t is put on its side (s_t) and
+// summed, the 64 partial sums meet in hs_wave_sum and m is the normalised sum.  Pass 2: the angle of conj(m) (x) d_t per frame (the
+// rows are read and d_t is formed again, by the same expressions), its mean, and zeros for the frames t >= n of angle.
+__global__ __launch_bounds__(HS_THREADS) void k_head_rot_cost(const float* __restrict__ feats, int rot6d, int F,
+                                                              const float* __restrict__ dev_quat, const int32_t* __restrict__ lengths,
+                                                              int WK, int K, int T, float* __restrict__ cost, float* __restrict__ angle) {
+    const int lane = threadIdx.x & 63;
+    const int wk = blockIdx.x * HS_WAVES + (threadIdx.x >> 6);         // uniform over the wave
+    if (wk >= WK) return;
+    const int w = wk / K;
+    const int n = min(max(lengths[w], 0), T);
+    float* ang = angle ? angle + (size_t)wk * T : nullptr;
+    if (n <= 1) {
+        if (lane == 0) cost[wk] = 0.f;
+        if (ang)
+            for (int t = lane; t < T; t += 64) ang[t] = 0.f;
+        return;
+    }
+    const float* f = feats + (size_t)wk * T * F;
+    const float* q = dev_quat + (size_t)w * T * 4;
+    auto seen = [&](int t) {
+        const float* b = q + (size_t)t * 4;
+        return rec_mul(rec_conj(hs_head_quat(f + (size_t)t * F, rot6d != 0)), RecQuat{b[0], b[1], b[2], b[3]});
+    };
+    const RecQuat first = lane < n ? seen(lane) : RecQuat{0.f, 0.f, 0.f, 0.f};
+    const RecQuat d0 = hs_shfl(first, 0);                             // n >= 2: lane 0 owns frame 0
+    RecQuat m = {0.f, 0.f, 0.f, 0.f};
+    for (int t = lane; t < n; t += 64) {
+        const RecQuat d = t == lane ? first : seen(t);
+        const float s = d.w * d0.w + d.x * d0.x + d.y * d0.y + d.z * d0.z < 0.f ? -1.f : 1.f;
+        m.w += s * d.w; m.x += s * d.x; m.y += s * d.y; m.z += s * d.z;
+    }
+    m = rec_normalize({hs_wave_sum(m.w), hs_wave_sum(m.x), hs_wave_sum(m.y), hs_wave_sum(m.z)});
+    const RecQuat mc = rec_conj(m);
+    float s = 0.f;
+    for (int t = lane; t < n; t += 64) {
+        const RecQuat r = rec_mul(mc, t == lane ? first : seen(t));
+        const float a = 2.f * atan2f(sqrtf(r.x * r.x + r.y * r.y + r.z * r.z), fabsf(r.w)) * 57.29577951308232f;
+        s += a;
+        if (ang) ang[t] = a;
+    }
+    if (ang)
+        for (int t = n + lane; t < T; t += 64) ang[t] = 0.f;
+    s = hs_wave_sum(s);
+    if (lane == 0) cost[wk] = s / (float)n;
+}
+
+extern "C" int seeme_head_rot_cost(const float* feats, int layout, int F, const float* dev_quat, const int32_t* lengths, int W, int K,
+                                   int T, float* cost, float* angle, void* stream) {
+    if (W < 1 || W > 65536) return seeme_fail("head_rot_cost: W must be in 1..65536");
+    if (K < 1 || K > HS_KMAX) return seeme_fail("head_rot_cost: K must be in 1..32");
+    if (T < 1 || T > (1 << 20)) return seeme_fail("head_rot_cost: T must be in 1..2^20");
+    bool ok = false;                                                  // the chain ends at joint 15: 16 joint rotations at least
+    if (layout == SEEME_STITCH_ROT6D) ok = F == 144;
+    else if (layout == SEEME_STITCH_ANGLE) ok = F % 3 == 0 && F >= 3 * (SEEME_HEAD_JOINT + 1);
+    else if (layout == SEEME_STITCH_ANGLE_TRANSL) ok = F % 3 == 0 && F >= 3 * (SEEME_HEAD_JOINT + 1) + 3;
+    if (!ok) {
+        char msg[256];
+        snprintf(msg, sizeof(msg), "head_rot_cost: layout %d with F = %d: expected SEEME_STITCH_ANGLE (0) with F = J x 3, "
+                 "SEEME_STITCH_ANGLE_TRANSL (1) with F = J x 3 + 3 (J >= 16), or SEEME_STITCH_ROT6D (2) with F = 144", layout, F);
+        return seeme_fail(msg);
+    }
+    if (!feats || !dev_quat || !lengths || !cost) return seeme_fail("head_rot_cost: null pointer");
+    if (((uintptr_t)feats | (uintptr_t)dev_quat | (uintptr_t)lengths | (uintptr_t)cost | (uintptr_t)angle) & 3)
+        return seeme_fail("head_rot_cost: every pointer must be 4-byte aligned");
+    const int WK = W * K;
+    hipLaunchKernelGGL(k_head_rot_cost, dim3((WK + HS_WAVES - 1) / HS_WAVES), dim3(HS_THREADS), 0, (hipStream_t)stream, feats,
+                       layout == SEEME_STITCH_ROT6D ? 1 : 0, F, dev_quat, lengths, WK, K, T, cost, angle);
+    return seeme_check_launch("k_head_rot_cost");
 }
 
 // ------------------------------------------------------------------ anchoring the stitched motion to the device's path

@@ -217,41 +217,7 @@ extern "C" int seeme_path_select(const float* cost, const float* unary, int W, i
 // Frame n belongs to window w = min(n / S, W-1), S = T - O, at local frame t = n - w*S; when w >= 1 and t < O it is also frame t + S
 // of window w-1 and the two are blended with weight u = (t+1)/(O+1) for window w, otherwise the unit is copied.
 // (RecQuat, rec_normalize, rec_aa_to_quat, rec_quat_to_aa and rec_blend: rec_quat.hpp, shared with track.hip)
-// model-side rot6d (geometry.rot6d_to_rotmat 'prohmr'): a1 = x[0:3], a2 = x[3:6], Gram-Schmidt, columns b1, b2, b1 x b2
-__device__ __forceinline__ RecQuat rec_rot6d_to_quat(const float* x) {
-    const float n1 = fmaxf(sqrtf(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]), 1e-12f);
-    const float b1[3] = {x[0] / n1, x[1] / n1, x[2] / n1};
-    const float dd = b1[0] * x[3] + b1[1] * x[4] + b1[2] * x[5];
-    const float u[3] = {x[3] - dd * b1[0], x[4] - dd * b1[1], x[5] - dd * b1[2]};
-    const float n2 = fmaxf(sqrtf(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]), 1e-12f);
-    const float b2[3] = {u[0] / n2, u[1] / n2, u[2] / n2};
-    const float b3[3] = {b1[1] * b2[2] - b1[2] * b2[1], b1[2] * b2[0] - b1[0] * b2[2], b1[0] * b2[1] - b1[1] * b2[0]};
-    // R[r][c]: column 0 = b1, 1 = b2, 2 = b3; the largest of w, x, y, z first (Shepperd)
-    const float m00 = b1[0], m10 = b1[1], m20 = b1[2], m01 = b2[0], m11 = b2[1], m21 = b2[2], m02 = b3[0], m12 = b3[1], m22 = b3[2];
-    const float tr = m00 + m11 + m22;
-    RecQuat q;
-    if (tr > 0.f) {
-        const float s = sqrtf(tr + 1.f) * 2.f;
-        q = {0.25f * s, (m21 - m12) / s, (m02 - m20) / s, (m10 - m01) / s};
-    } else if (m00 > m11 && m00 > m22) {
-        const float s = sqrtf(1.f + m00 - m11 - m22) * 2.f;
-        q = {(m21 - m12) / s, 0.25f * s, (m01 + m10) / s, (m02 + m20) / s};
-    } else if (m11 > m22) {
-        const float s = sqrtf(1.f + m11 - m00 - m22) * 2.f;
-        q = {(m02 - m20) / s, (m01 + m10) / s, 0.25f * s, (m12 + m21) / s};
-    } else {
-        const float s = sqrtf(1.f + m22 - m00 - m11) * 2.f;
-        q = {(m10 - m01) / s, (m02 + m20) / s, (m12 + m21) / s, 0.25f * s};
-    }
-    return rec_normalize(q);
-}
-
-__device__ __forceinline__ void rec_quat_to_rot6d(RecQuat q, float* x) {             // the first two columns of the rotation matrix
-    const float w = q.w, a = q.x, b = q.y, c = q.z;
-    x[0] = 1.f - 2.f * (b * b + c * c); x[1] = 2.f * (a * b + w * c); x[2] = 2.f * (a * c - w * b);
-    x[3] = 2.f * (a * b - w * c); x[4] = 1.f - 2.f * (a * a + c * c); x[5] = 2.f * (b * c + w * a);
-}
-
+// (rec_rot6d_to_quat and rec_quat_to_rot6d, the model-side rot6d: rec_quat.hpp as well, shared with headset.hip)
 __global__ __launch_bounds__(REC_THREADS) void k_stitch_windows(const float* __restrict__ feats, int W, int T, int O, int n_frames,
                                                                 int F, int layout, float* __restrict__ out) {
     const int rot6d = layout == SEEME_STITCH_ROT6D;

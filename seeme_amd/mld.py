@@ -48,6 +48,7 @@ from .hyp_metrics import (K_MAX, HypothesisMetrics, SelectionMetrics, best_index
                           keep_mask, select_index)
 from .mesh_metrics import COLLISION_HYP, COLLISION_REF, CollisionMetrics, MeshMetrics, check_closed_faces, mesh_metrics_eval
 from .resnet import ResNet50
+from .recording import check_head_offset
 from .respointnet import ResnetPointnet
 from .shapes import motion_layout
 from .smpl import SMPL
@@ -401,6 +402,17 @@ class MLD(nn.Module):
         if not isinstance(self.head_anchor, bool):
             raise ValueError(f"TEST.HEAD_ANCHOR must be true or false, got {self.head_anchor!r}")
         self.head_anchor_sigma = check_sigma(cfg.TEST.get("HEAD_ANCHOR_SIGMA", DEFAULT_SIGMA), "TEST.HEAD_ANCHOR_SIGMA")
+        # the headset's orientation (predict_recording with head_rot): the weight of the head-rotation term of the unary (mm per degree;
+        # 0: off; no value has been measured on data), whether the stitched motion's deviation per frame is reported, and the vector
+        # from joint 15 to the device in the device's frame (metres; zeros: the device's path is taken as the joint's)
+        self.path_head_rot_weight = cfg.TEST.get("PATH_HEAD_ROT_WEIGHT", 0.0)
+        if isinstance(self.path_head_rot_weight, bool) or not isinstance(self.path_head_rot_weight, (int, float)) \
+                or not 0 <= self.path_head_rot_weight < float("inf"):
+            raise ValueError(f"TEST.PATH_HEAD_ROT_WEIGHT must be a finite number >= 0, got {self.path_head_rot_weight!r}")
+        self.head_rot_report = cfg.TEST.get("HEAD_ROT_REPORT", False)
+        if not isinstance(self.head_rot_report, bool):
+            raise ValueError(f"TEST.HEAD_ROT_REPORT must be true or false, got {self.head_rot_report!r}")
+        self.head_device_offset = check_head_offset(cfg.TEST.get("HEAD_DEVICE_OFFSET", (0.0, 0.0, 0.0)), "TEST.HEAD_DEVICE_OFFSET")
         # the body against the scene (predict_recording with scene_cloud): the weight of the body-scene term of the unary (0: off),
         # whether the stitched motion's depth per frame is reported, and the quantile of the default capsules' radii
         self.path_scene_weight = cfg.TEST.get("PATH_SCENE_WEIGHT", 0.0)
@@ -1328,7 +1340,8 @@ class MLD(nn.Module):
     @torch.no_grad()
     def predict_recording(self, batch_of_windows, n_frames, overlap=None, betas=None, medoid_weight=None, num_hypotheses=None,
                           latents=None, cond_noise=None, step_noise=None, window_frames=None, head_path=None, head_weight=None,
-                          head_anchor=None, anchor_sigma=None, scene_cloud=None, scene_weight=None, scene_report=None, capsules=None):
+                          head_anchor=None, anchor_sigma=None, scene_cloud=None, scene_weight=None, scene_report=None, capsules=None,
+                          head_rot=None, head_rot_weight=None, head_rot_report=None, head_offset=None):
         """One motion for a recording of `n_frames` frames.  The batch rows are its W windows (``recording.window_plan`` of n_frames,
         the batch's T and `overlap`; ``recording.windows_batch`` builds them), all in ONE coordinate frame unless `window_frames` says
         otherwise: the seam cost compares global joint positions (GIMO scenes are in one frame already; a moving camera: below).  Steps: ``predict`` (K hypotheses per window) -> ``overlap_cost`` -> unary[w,k] = medoid_weight x
@@ -1355,7 +1368,21 @@ class MLD(nn.Module):
         stitched motion's head onto the path: shift, residual = ``head_anchor`` of the stitched joints with the taps of anchor_sigma
         (None = TEST.HEAD_ANCHOR_SIGMA); joints and, where the features carry one, the motion's translation move by shift, and the
         result gains head_shift [n_frames,3], head_residual [n_frames] (mm) and transl [n_frames,3] (the motion's translation, or
-        the shift alone for features without one).  The device sits a few centimetres from joint 15; that lever arm is not modelled.
+        the shift alone for features without one).
+
+        head_rot [n_frames,3,3]: the headset's orientation in every frame, the rotation device -> the frame the seams are compared in
+        (``recording.camera_rotations`` of world2cam, or the recording's head_rot).  Given alone it changes nothing and launches
+        nothing.  head_rot_weight (None = TEST.PATH_HEAD_ROT_WEIGHT, 0) > 0 adds head_rot_weight x the cost of
+        ``recording.head_rot_cost_hip`` (degrees: how far a hypothesis' head turns against the device over its window, a constant
+        mount rotation removed; the weight is mm per degree and no value has been measured) to the unary.  It reads the features'
+        joint rotations alone (m_rst_all, in the windows' own frames, against ``recording.head_rot_windows`` with window_frames), so
+        it serves every layout, rot6d and features without a translation included; the result gains head_rot_cost [W,K] and
+        head_rot_cost_path [W].  head_rot_report (None = TEST.HEAD_ROT_REPORT, false) runs the kernel once on the stitched motion as
+        one row of n_frames frames; the result gains head_rot_residual [n_frames] (degrees per frame from the recording's one mean
+        mount rotation) and head_rot_mean (their mean).  head_offset [3] (None = TEST.HEAD_DEVICE_OFFSET, zeros): the vector from
+        joint 15 to the device in the device's frame, metres (``recording.fit_device_offset``).  When it is not zero, head_path is
+        replaced by ``recording.head_joint_path`` (head_path[n] - C_n offset, the lever arm, which turns with the head) before
+        head_weight and head_anchor use it; it needs head_rot.
 
         scene_cloud [N,3]: the scene's points in the frame the seams are compared in (the world frame with window_frames).  Given
         alone it changes nothing and launches nothing.  scene_weight (None = TEST.PATH_SCENE_WEIGHT, 0) > 0 adds scene_weight x the
@@ -1395,6 +1422,20 @@ class MLD(nn.Module):
             raise ValueError("predict_recording: head_weight (TEST.PATH_HEAD_WEIGHT) > 0 needs features that carry a translation "
                              "(TRAIN.ABLATION.PREDICT_TRANSL, not rot6d): these hypotheses have no global position to compare with the "
                              "headset's path; head_anchor places them")
+        hrw = self.path_head_rot_weight if head_rot_weight is None else head_rot_weight
+        if isinstance(hrw, bool) or not isinstance(hrw, (int, float)) or not 0 <= hrw < float("inf"):
+            raise ValueError(f"head_rot_weight must be a finite number >= 0, got {hrw!r}")
+        rot_report = self.head_rot_report if head_rot_report is None else head_rot_report
+        if not isinstance(rot_report, bool):
+            raise ValueError(f"head_rot_report must be true or false, got {rot_report!r}")
+        offset = self.head_device_offset if head_offset is None else check_head_offset(head_offset, "head_offset")
+        lever = bool((offset != 0).any())
+        if (hrw > 0 or rot_report or lever) and head_rot is None:
+            raise ValueError("predict_recording: head_rot_weight > 0, head_rot_report and a head_offset that is not zero need head_rot "
+                             "[n_frames,3,3], the headset's orientation in every frame (the recording's head_rot, or "
+                             "recording.camera_rotations of world2cam)")
+        rot = R.check_head_rot(head_rot, n_frames, "predict_recording") if hrw > 0 or rot_report or lever else None
+        rot_layout = R.stitch_layout(self.data_type, self.transl_in_feats)
         sw = self.path_scene_weight if scene_weight is None else scene_weight
         if isinstance(sw, bool) or not isinstance(sw, (int, float)) or not 0 <= sw < float("inf"):
             raise ValueError(f"scene_weight must be a finite number >= 0, got {sw!r}")
@@ -1420,6 +1461,8 @@ class MLD(nn.Module):
             if tuple(hp.shape) != (n_frames, 3) or not hp.dtype.is_floating_point:
                 raise ValueError(f"predict_recording: head_path is {tuple(hp.shape)} {hp.dtype}: expected floats [n_frames,3] = "
                                  f"[{n_frames},3]")
+            if lever:                                                          # the device's path -> the path of joint 15 itself
+                hp = torch.from_numpy(R.head_joint_path(hp, rot, offset))
             hp = hp.to(device=dev, dtype=torch.float32).contiguous()
         if betas is not None:
             betas = torch.as_tensor(betas, device=dev, dtype=torch.float32)
@@ -1446,6 +1489,11 @@ class MLD(nn.Module):
         if hw > 0:                                                             # (jts: the frame the path is in)
             head_cost = R.head_path_cost_hip(jts.contiguous(), R.head_path_windows(hp, starts, lens, int(jts.shape[2])), lens)
             unary = float(hw) * head_cost if unary is None else unary + float(hw) * head_cost
+        head_rot_cost = None
+        if hrw > 0:                                                            # (m_rst_all: the windows' own frames)
+            dq = R.head_rot_windows(rot, starts, lens, int(pr["m_rst_all"].shape[2]), window_frames=Mw if window_frames is not None else None)
+            head_rot_cost = R.head_rot_cost_hip(pr["m_rst_all"].contiguous(), rot_layout, dq.to(dev), lens)["cost"]
+            unary = float(hrw) * head_rot_cost if unary is None else unary + float(hrw) * head_rot_cost
         scene = None
         if cloud is not None:
             if capsules is None:                                               # (rot6d is posed with zero betas)
@@ -1486,6 +1534,13 @@ class MLD(nn.Module):
                 motion[:, -3:] += shift
             out["head_shift"], out["head_residual"] = shift, residual
             out["transl"] = motion[:, -3:].clone() if self.transl_in_feats else shift
+        if head_rot_cost is not None:
+            out["head_rot_cost"] = head_rot_cost
+            out["head_rot_cost_path"] = head_rot_cost[torch.arange(W, device=dev), sel["path"]]
+        if rot_report:                                                         # the stitched motion as one row of n_frames frames
+            turned = R.head_rot_cost_hip(motion[None, None].contiguous(), rot_layout, R.head_rot_windows(rot, [0], [n_frames], n_frames).to(dev),
+                                         [n_frames])
+            out["head_rot_residual"], out["head_rot_mean"] = turned["angle"][0, 0], turned["cost"][0, 0]
         if scene is not None:
             out["scene_cost"], out["scene_hits"] = scene["cost"], scene["hits"]
             out["scene_cost_path"] = scene["cost"][torch.arange(W, device=dev), sel["path"]]

@@ -21,6 +21,10 @@ The model sees clips of T frames; a recording is cut into W overlapping windows 
                        headset's own path over its window, the mean offset removed: a unary term of ``path_select``.
 ``head_anchor_hip``    ``seeme_head_anchor``: the smoothed shift [L,3] that puts the stitched motion's head onto the headset's path,
                        and what is left per frame (mm).  ``camera_centres`` / ``head_path_windows`` prepare the path on the host.
+``head_rot_cost_hip``  ``seeme_head_rot_cost``: cost [W,K] (degrees), how far a hypothesis' head (the chain 0-3-6-9-12-15) turns against
+                       the headset's orientation over its window, a constant mount rotation removed: a unary term as well, and the
+                       angle per frame.  ``camera_rotations`` / ``head_rot_windows`` prepare the quaternions on the host;
+                       ``head_joint_path`` / ``fit_device_offset`` are the lever arm between joint 15 and the device.
 ``scene_depth_hip``    ``seeme_scene_depth``: depth [W,K,T] (mm), how deep the capsules round a hypothesis' bones (``body_capsules``)
                        reach into the scene's points, its mean cost [W,K] (a unary term of ``path_select``) and the count of
                        penetrating frames hits [W,K]; ``scene_depth_torch`` is its twin.
@@ -312,6 +316,162 @@ def head_anchor_torch(joints, path, taps) -> Tuple[torch.Tensor, torch.Tensor]:
         wsum = wsum + k
     shift = acc / wsum[:, None]
     return shift, 1000.0 * (r - shift).norm(dim=-1)
+
+
+# ----------------------------------------------------------------------------- the headset's orientation: host side and the twin
+def camera_rotations(world2cam) -> np.ndarray:
+    """world2cam [L,4,4], the rigid maps p -> A_n p + a_n -> float64 [L,3,3]: A_n^T, the rotation camera -> world of every frame, the
+    device's orientation in the world frame.  Which way the camera's axes point does not matter to ``head_rot_cost``: a constant
+    rotation on the device's side costs nothing."""
+    M = np.asarray(world2cam, np.float64)
+    if M.ndim != 3 or M.shape[1:] != (4, 4):
+        raise ValueError(f"camera_rotations: world2cam is {M.shape}: expected [L,4,4]")
+    return np.ascontiguousarray(M[:, :3, :3].transpose(0, 2, 1))
+
+
+def check_head_rot(rot, n_frames: int, what: str = "head_rot") -> np.ndarray:
+    """head_rot -> float64 [L,3,3], the rotations device -> world: floats, finite, orthonormal to 1e-3 with a positive determinant (as
+    ``check_world2cam`` asks of its 3x3 block), one per recording frame, or a ValueError that names the key and the frame."""
+    a = rot.detach().cpu().numpy() if isinstance(rot, torch.Tensor) else np.asarray(rot)
+    if a.dtype.kind != "f" or a.shape != (n_frames, 3, 3):
+        raise ValueError(f"{what}: head_rot is {a.shape} {a.dtype}: expected floats [{n_frames},3,3] (L = {n_frames}), the rotation "
+                         "device -> world of every frame")
+    a = np.ascontiguousarray(a, np.float64)
+    bad = ~np.isfinite(a).all(axis=(1, 2))
+    with np.errstate(invalid="ignore"):
+        bad |= ~(np.abs(a.transpose(0, 2, 1) @ a - np.eye(3)).max(axis=(1, 2)) <= 1e-3) | ~(np.linalg.det(np.nan_to_num(a)) > 0)
+    if bad.any():
+        f = int(np.argmax(bad))
+        raise ValueError(f"{what}: head_rot of frame {f} is not a rotation (finite, orthonormal to 1e-3, a positive determinant):\n{a[f]}")
+    return a
+
+
+def _rot3(rot, name: str) -> np.ndarray:
+    a = np.asarray(rot.detach().cpu().numpy() if isinstance(rot, torch.Tensor) else rot, np.float64)
+    if a.ndim != 3 or a.shape[1:] != (3, 3):
+        raise ValueError(f"{name}: the rotations are {a.shape}: expected [L,3,3]")
+    return a
+
+
+def head_rot_windows(rot, starts, lengths, T: int, window_frames=None) -> torch.Tensor:
+    """rot [L,3,3] (device -> world) -> float32 [W,T,4] on the host: row w holds the unit quaternions (w,x,y,z) of
+    rot[starts[w] : starts[w] + lengths[w]], then identities: the dev_quat operand of ``head_rot_cost`` for the windows of
+    ``window_plan``.  window_frames [W,4,4] (M_w, world -> window w's frame): the rotations are moved into every window's own frame
+    first, A_w C_n with A_w the rotation block of M_w -- the frame ``predict``'s m_rst_all is in.  Computed in float64."""
+    C = _rot3(rot, "head_rot_windows")
+    T = int(T)
+    A = None
+    if window_frames is not None:
+        A = np.asarray(window_frames.detach().cpu().numpy() if isinstance(window_frames, torch.Tensor) else window_frames, np.float64)
+        if A.shape != (len(starts), 4, 4):
+            raise ValueError(f"head_rot_windows: window_frames are {A.shape}: expected [W,4,4] = [{len(starts)},4,4]")
+    out = torch.zeros(len(starts), T, 4, dtype=torch.float64)
+    out[..., 0] = 1.0
+    for w, (lo, ln) in enumerate(zip(starts, lengths)):
+        lo, ln = int(lo), int(ln)
+        if lo < 0 or ln < 0 or ln > T or lo + ln > C.shape[0]:
+            raise ValueError(f"head_rot_windows: window {w} (frames {lo}..{lo + ln - 1}) does not fit T = {T} and {C.shape[0]} rotations")
+        if ln:
+            Cw = C[lo:lo + ln] if A is None else A[w, :3, :3][None] @ C[lo:lo + ln]
+            out[w, :ln] = G.rotmat_to_quat_torch(torch.from_numpy(np.ascontiguousarray(Cw)))
+    return out.float()
+
+
+def check_head_offset(offset, what: str = "head_offset") -> np.ndarray:
+    """The vector from joint 15 to the device in the device's frame, metres -> float64 [3]: three finite numbers, or a ValueError that
+    names `what`."""
+    vals = offset.detach().cpu().reshape(-1).tolist() if isinstance(offset, torch.Tensor) else offset
+    try:
+        vals = list(vals)
+    except TypeError:
+        vals = None
+    if vals is None or len(vals) != 3 or any(isinstance(v, (bool, str)) or not isinstance(v, (int, float, np.integer, np.floating))
+                                             or not np.isfinite(v) for v in vals):
+        raise ValueError(f"{what} must be three finite numbers (x, y, z in metres, in the device's frame), got {offset!r}")
+    return np.array([float(v) for v in vals], np.float64)
+
+
+def head_joint_path(path, rot, offset) -> np.ndarray:
+    """The lever arm: path [L,3] (the device's positions), rot [L,3,3] (device -> the frame the path is in), offset [3] (the vector
+    from joint 15 to the device, metres, in the device's frame) -> float64 [L,3], path[n] - C_n offset: the path of joint 15 itself,
+    which both head terms take in place of the device's."""
+    C = _rot3(rot, "head_joint_path")
+    p = np.asarray(path.detach().cpu().numpy() if isinstance(path, torch.Tensor) else path, np.float64)
+    o = np.asarray(offset.detach().cpu().numpy() if isinstance(offset, torch.Tensor) else offset, np.float64)
+    if p.shape != (C.shape[0], 3) or o.shape != (3,) or not np.isfinite(o).all():
+        raise ValueError(f"head_joint_path: the path is {p.shape}, the offset {o.shape}: expected [{C.shape[0]},3] and 3 finite numbers")
+    return p - np.einsum("nij,j->ni", C, o)
+
+
+def fit_device_offset(head, path, rot) -> Tuple[np.ndarray, float]:
+    """head [L,3] (joint 15 of a KNOWN wearer), path [L,3] (the device), rot [L,3,3] (device -> their frame) -> (offset [3] float64 in
+    the device's frame, rms_mm): the least-squares offset mean_n C_n^T (path_n - head_n) and the RMS of what it leaves, mm."""
+    C = _rot3(rot, "fit_device_offset")
+    h, p = (np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, np.float64) for a in (head, path))
+    if h.shape != (C.shape[0], 3) or p.shape != h.shape or C.shape[0] < 1:
+        raise ValueError(f"fit_device_offset: head is {h.shape}, the path {p.shape}, the rotations {C.shape}: expected [L,3], [L,3] and "
+                         "[L,3,3], L >= 1")
+    offset = np.einsum("nji,nj->ni", C, p - h).mean(axis=0)
+    left = p - h - np.einsum("nij,j->ni", C, offset)
+    return offset, 1000.0 * float(np.sqrt((left * left).sum(axis=1).mean()))
+
+
+def _quat_mul(p, q):
+    pw, px, py, pz = p.unbind(-1)
+    qw, qx, qy, qz = q.unbind(-1)
+    return torch.stack([pw * qw - px * qx - py * qy - pz * qz, pw * qx + px * qw + py * qz - pz * qy,
+                        pw * qy - px * qz + py * qw + pz * qx, pw * qz + px * qy - py * qx + pz * qw], dim=-1)
+
+
+def _quat_conj(q):
+    return torch.cat([q[..., :1], -q[..., 1:]], dim=-1)
+
+
+def _check_head_rot_cost(feats, layout, dev_quat, lengths):
+    if not isinstance(feats, torch.Tensor) or not isinstance(dev_quat, torch.Tensor) or not feats.dtype.is_floating_point \
+            or dev_quat.dtype != feats.dtype:
+        raise ValueError(f"head_rot_cost: features and dev_quat must be float tensors of one dtype, got {getattr(feats, 'dtype', type(feats))} "
+                         f"and {getattr(dev_quat, 'dtype', type(dev_quat))}")
+    if feats.dim() != 4 or tuple(dev_quat.shape) != (feats.shape[0], feats.shape[2], 4):
+        raise ValueError(f"head_rot_cost: features are {tuple(feats.shape)}, dev_quat is {tuple(dev_quat.shape)}: expected [W,K,T,F] and "
+                         "[W,T,4]")
+    F = int(feats.shape[3])
+    if isinstance(layout, bool) or not isinstance(layout, (int, np.integer)) or layout not in (STITCH_ANGLE, STITCH_ANGLE_TRANSL, STITCH_ROT6D) \
+            or not (F == 144 if layout == STITCH_ROT6D else F % 3 == 0 and F // 3 - (layout == STITCH_ANGLE_TRANSL) >= HEAD_JOINT + 1):
+        raise ValueError(f"head_rot_cost: layout {layout!r} with features {F} wide: expected STITCH_ANGLE with J x 3, STITCH_ANGLE_TRANSL "
+                         "with J x 3 + 3 (J >= 16) or STITCH_ROT6D with 144")
+    n = lengths.detach().cpu().reshape(-1).tolist() if isinstance(lengths, torch.Tensor) else [v for v in lengths]
+    if len(n) != feats.shape[0] or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in n):
+        raise ValueError(f"head_rot_cost: lengths are {n!r}: expected {feats.shape[0]} integers, one per window")
+    return [int(v) for v in n]
+
+
+def head_rot_cost_torch(feats, layout: int, dev_quat, lengths) -> Dict[str, torch.Tensor]:
+    """feats [W,K,T,F] renormed features, dev_quat [W,T,4], lengths [W] (integers), any float dtype, any device, any K ->
+    {"cost" [W,K], "angle" [W,K,T]} (degrees): the definition of ``seeme_head_rot_cost``.  Frames past a window's length, joints off
+    the chain 0-3-6-9-12-15 and the translation columns take no part (a NaN there is not seen)."""
+    n = _check_head_rot_cost(feats, layout, dev_quat, lengths)
+    W, K, T = (int(v) for v in feats.shape[:3])
+    dev, dt = feats.device, feats.dtype
+    nn = torch.tensor(n, device=dev).clamp(0, T)
+    keep = (torch.arange(T, device=dev)[None] < nn[:, None])[:, None, :]                               # [W,1,T]
+    uw = 6 if layout == STITCH_ROT6D else 3
+    unit = torch.tensor([1.0, 0, 0, 0, 1.0, 0] if uw == 6 else [0.0, 0, 0], device=dev, dtype=dt)      # the identity, where not kept
+    to_quat = _rot6d_to_quat if uw == 6 else _aa_to_quat
+    h = None
+    for j in range(0, HEAD_JOINT + 1, 3):                                                              # the chain 0, 3, 6, 9, 12, 15
+        q = to_quat(torch.where(keep[..., None], feats[..., uw * j:uw * j + uw], unit))
+        h = q if h is None else _quat_mul(h, q)
+    one = torch.tensor([1.0, 0, 0, 0], device=dev, dtype=dt)
+    d = _quat_mul(_quat_conj(h), torch.where(keep[..., None], dev_quat[:, None], one))                 # [W,K,T,4]
+    s = torch.where((d * d[:, :, :1]).sum(-1, keepdim=True) < 0, -1.0, 1.0).to(dt) * keep[..., None].to(dt)
+    m = (s * d).sum(dim=2)
+    live = (nn > 1)[:, None]                                                                           # [W,1]
+    m = _normalize(torch.where(live[..., None], m, one))
+    r = _quat_mul(_quat_conj(m)[:, :, None], d)
+    a = 2.0 * torch.atan2(r[..., 1:].norm(dim=-1), r[..., 0].abs()) * (180.0 / np.pi)
+    a = torch.where(keep & live[..., None], a, torch.zeros((), device=dev, dtype=dt))
+    return {"cost": a.sum(dim=2) / nn.clamp(min=1).to(dt)[:, None], "angle": a}
 
 
 # ----------------------------------------------------------------------------- the body against the scene: capsules and the twin
@@ -636,6 +796,30 @@ def _launch_head_anchor(joints, path, n_frames, taps, Rr, out=None):
     return out
 
 
+def head_rot_cost_hip(feats, layout: int, dev_quat, lengths) -> Dict[str, torch.Tensor]:
+    """feats [W,K,T,F] renormed features, dev_quat [W,T,4] fp32 on the device, K <= 32 (``head_rot_cost_torch`` serves K > 32), lengths
+    [W] integers -> {"cost" [W,K], "angle" [W,K,T]} (degrees) (``seeme_head_rot_cost``).  Launches on the current stream."""
+    n = _check_head_rot_cost(feats, layout, dev_quat, lengths)
+    if feats.dtype != torch.float32:
+        raise ValueError(f"head_rot_cost: features and dev_quat must be float32, got {feats.dtype}")
+    L.require_cuda(feats, "feats")
+    L.require_cuda(dev_quat, "dev_quat")
+    W, K, T, F = (int(v) for v in feats.shape)
+    len32 = torch.tensor(n, dtype=torch.int64).clamp(-1, T).to(device=feats.device, dtype=torch.int32)
+    return _launch_head_rot_cost(feats.contiguous(), int(layout), F, dev_quat.contiguous(), len32, W, K, T)
+
+
+def _launch_head_rot_cost(feats, layout, F, dev_quat, len32, W, K, T, out=None) -> Dict[str, torch.Tensor]:
+    """out: {"cost", "angle"} to write into (the tests' slots; "angle" None: not written); None operands travel as null pointers."""
+    if out is None:
+        dev = next(t for t in (feats, dev_quat, len32) if t is not None).device
+        out = {"cost": torch.empty(max(W, 0), max(K, 0), device=dev, dtype=torch.float32),
+               "angle": torch.empty(max(W, 0), max(K, 0), max(T, 0), device=dev, dtype=torch.float32)}
+    L.call("seeme_head_rot_cost", L.ptr(feats), layout, F, L.ptr(dev_quat), L.ptr(len32), W, K, T, L.ptr(out["cost"]),
+           L.ptr(out.get("angle")), L.current_stream())
+    return out
+
+
 def scene_depth_hip(jts, lengths, points, segs, radius) -> Dict[str, torch.Tensor]:
     """jts [W,K,T,J,3], points [N,3] fp32 on the device, lengths [W] integers (an int32 tensor on the device is taken as it is),
     segs [NB,2] and radius [NB] on the host (NB <= 32, indices below J, radii finite and >= 0: the library validates them) ->
@@ -840,7 +1024,8 @@ def load_recording(path: str, video: Optional[str] = None, require_interactee: b
     it is composed and inverted), and, in place of scene, scene_vertices [N,3]: the scene's vertices in the world frame, from which
     every window's view is selected (``scene_views_hip``).  head_path [L,3] (floats, finite; returned float64) is the device's position
     in the world frame; when present it is used instead of the centres of world2cam (``camera_centres``), and it also serves
-    recordings in one fixed frame that have no world2cam.
+    recordings in one fixed frame that have no world2cam.  head_rot [L,3,3] (floats, rotations to 1e-3; returned float64) is the device's
+    orientation, device -> world, in the same way: used instead of the rotations of world2cam (``camera_rotations``) when present.
 
     The image condition has ONE source: image_feats, or video [Lf,H,W,3] uint8 RGB (decoded frames; needs center [L,2] and scale
     [L], the interactee's box per recording frame, ``crops.patch_box``), or image_crops [Lf,224,224,3] uint8 (patches already cut).
@@ -869,6 +1054,7 @@ def load_recording(path: str, video: Optional[str] = None, require_interactee: b
         if "world2cam" in z.files:
             rec["world2cam"] = np.asarray(z["world2cam"], np.float64)
         head_path = z["head_path"] if "head_path" in z.files else None
+        head_rot = z["head_rot"] if "head_rot" in z.files else None
         rec.update({k: z[k] for k in _FRAME_KEYS if k in z.files})
     if video is not None:
         if "video" in rec:
@@ -898,6 +1084,8 @@ def load_recording(path: str, video: Optional[str] = None, require_interactee: b
         check_world2cam(rec["world2cam"], n, path)
     if head_path is not None:
         rec["head_path"] = check_head_path(head_path, n, path)
+    if head_rot is not None:
+        rec["head_rot"] = check_head_rot(head_rot, n, path)
     if not require_interactee:
         _check_estimate_input(rec, n, path, bool(allow_sparse))
     rec["n_frames"] = n
